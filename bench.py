@@ -13,11 +13,19 @@ time is the max over ranks.
 this script as a CHILD process (nothing touches the GPU in the parent) and relays rank 0's line, as the
 reference's ``accelerate launch --multi_gpu`` (script/distil_whisper_v2.0.sh:26) starts one process per GPU.
 
-Prints ONE JSON line (rank 0).  Extra fields: ``roofline`` of the decode attention (the cross-attention's
-K/V stream, HBM-bound), ``encoder_mfma`` (encoder MFMA fraction), ``decode_kernel_us``
-(per-launch time of each decode-step kernel in step context, eager: an upper bound that includes the
-dispatch gap; the rocprofv3 trace in profiles/ gives the device times), ``cpu_baseline`` (reference
-transformers path on the host cores, bounded sample).
+Prints ONE JSON line (rank 0).  A plain run (``--gpus 1 --steps N --warmup W``) does only what the headline
+figure needs: set up, warm up, time the N steps, print the line (``value``, ``ms_per_step`` and the run's
+configuration).  ``--dump-outputs DIR`` also writes what the last timed step returned to its caller, the
+generated token ids, as ``DIR/token_ids.npy`` (float32; under ``--gpus N`` one ``token_ids_rank<r>.npy`` per
+rank from the gather), so that two builds can be compared output for output: model, audio and arguments are
+seeded, hence identical from run to run.
+
+``--full`` adds the measurements that take runs of their own after the timed region: ``roofline`` of the decode
+attention (the cross-attention's K/V stream, HBM-bound), ``encoder_mfma`` (encoder MFMA fraction),
+``decode_step_ms``, ``decode_kernel_us`` (per-launch time of each decode-step kernel in step context, eager: an
+upper bound that includes the dispatch gap; the rocprofv3 trace in profiles/ gives the device times),
+``inflight`` (with ``--inflight``) and ``cpu_baseline`` (reference transformers path on the host cores, bounded
+sample; ``--no-cpu-baseline`` leaves it out).
 """
 from __future__ import annotations
 
@@ -115,7 +123,13 @@ def parse(argv=None):
     ap.add_argument("--batch", type=int, default=32)
     ap.add_argument("--max-length", type=int, default=128)
     ap.add_argument("--model", default="large-v3")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure what is not the headline value: the decode kernels one "
+                         "by one, the roofline of the cross-attention, the encoder's MFMA fraction, --inflight lanes "
+                         "and the CPU baseline.  Off by default: a plain run times its steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the token ids the last timed step returned as DIR/token_ids.npy (float32)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline leg")
     ap.add_argument("--cpu-batch", type=int, default=4)
     ap.add_argument("--cpu-threads", type=int, default=None)
     ap.add_argument("--kernel-iters", type=int, default=20)
@@ -127,7 +141,20 @@ def parse(argv=None):
     ap.add_argument("--stub", action="store_true",
                     help="no GPU work: each rank times a trivial host step (tests the launcher, barriers, "
                          "max-over-ranks timing and the ids gather on the CPU; with KW_BENCH_BACKEND=gloo)")
-    return ap.parse_args(argv)
+    a = ap.parse_args(argv)
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    if a.inflight and not a.full:
+        ap.error("--inflight is an extra measurement: it needs --full")
+    return a
+
+
+def dump_outputs(path: str, arrays: dict) -> None:
+    """``--dump-outputs``: one ``<name>.npy`` (float32; token ids are exact in it) per array the timed path
+    returned in its last step."""
+    os.makedirs(path, exist_ok=True)
+    for name, arr in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(arr, dtype=np.float32))
 
 
 def launch_ranks(a, argv) -> int:
@@ -188,6 +215,9 @@ def stub_main(a, world, rank, dist):
            "ms_per_step": dt / a.steps * 1e3, "stub": True,
            "dist": {"world": world, "backend": dist.get_backend() if dist is not None else None}}
     if rank == 0:
+        if a.dump_outputs:
+            dump_outputs(a.dump_outputs, {"token_ids": ids[-1].numpy()} if dist is None else
+                         {f"token_ids_rank{r}": g.numpy() for r, g in enumerate(gathered)})
         print(json.dumps(out), flush=True)
 
 
@@ -228,8 +258,6 @@ def main(argv=None):
     from kwhisper.feature_extraction import WhisperFeatureExtractor
     from kwhisper.generation import KWhisperForConditionalGeneration
     from kwhisper.synthetic import dummy_audio, synthetic_state_dict
-    from kwhisper import _lib as L
-    from kwhisper import ops
 
     shape = PRESETS[a.model]
     # the numpy recipe, seed 0: the random model tests/golden/large_v3_b32_fp32.npz pins (transformers fp32 on these
@@ -285,6 +313,50 @@ def main(argv=None):
     new_tokens = int(out_ids[-1].shape[1])
     if gathered is not None:
         assert len(gathered) == world and all(g.shape == gathered[0].shape for g in gathered)
+    ms_per_step = dt / a.steps * 1e3
+
+    result = {
+        "metric": "audio-seconds/sec (RTF) whisper-large-v3 30s@bs32",
+        "value": world * B * 30.0 * a.steps / dt,
+        "unit": "audio-s/s",
+        "n_gpus": world,
+        "steps": a.steps,
+        "warmup": a.warmup,
+        "ms_per_step": ms_per_step,
+        "higher_is_better": True,
+        "scaling": "weak",
+        "vs_baseline": None,
+        "dtype": "bf16",
+        "data": "synthetic (run_speed_eval.py noise audio, random-init large-v3 weights: kwhisper.synthetic numpy recipe seed 0, the config-3 fixture's model)",
+        "config": {"workload": "config 3: whisper-large-v3 greedy generate, 30 s clips, log-mel on GPU",
+                   "model": shape.name, "global_batch": B * world, "per_gpu_batch": B,
+                   "max_length": a.max_length, "new_tokens": new_tokens, "seq_len": 1500,
+                   "parallelism": f"dp{world}"},
+        "dist": {"world": world, "rank_device": local, "device_name": torch.cuda.get_device_name(dev),
+                 "backend": dist.get_backend() if use_dist else None,
+                 "ids_gather": "all_gather of the padded int32 token matrices, inside the timed region"
+                 if use_dist else None},
+    }
+    if rank == 0 and a.dump_outputs:  # what the last timed step handed its caller
+        dump_outputs(a.dump_outputs, {"token_ids": out_ids[-1].cpu().numpy()} if gathered is None else
+                     {f"token_ids_rank{r}": g[-1].cpu().numpy() for r, g in enumerate(gathered)})
+    if a.full:
+        result.update(full_measurements(a, model, fe, audio, gen_kw, out_ids, shape, dev, world, rank))
+    if rank == 0:
+        print(json.dumps(result), flush=True)
+    if use_dist:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+def full_measurements(a, model, fe, audio, gen_kw, out_ids, shape, dev, world, rank) -> dict:
+    """``--full``: what the bench reports beside its headline value, measured after the timed region (the
+    in-flight lanes, per-kernel and roofline figures with HIP events, the CPU baseline)."""
+    from kwhisper.generation import KWhisperForConditionalGeneration
+    from kwhisper import _lib as L
+    from kwhisper import ops
+
+    B = a.batch
 
     def inflight_rate(n_lanes, n_batches):
         """``n_lanes`` batches of B clips in flight at once (one thread, stream, model handle and decode session
@@ -407,29 +479,8 @@ def main(argv=None):
     enc_t = time_fn(lambda: eng.encode(feats), 3)
     step_graph = sess._graph
     step_t = time_fn(lambda: step_graph.replay(), iters) if step_graph is not None else None
-    ms_per_step = dt / a.steps * 1e3
 
     result = {
-        "metric": "audio-seconds/sec (RTF) whisper-large-v3 30s@bs32",
-        "value": world * B * 30.0 * a.steps / dt,
-        "unit": "audio-s/s",
-        "n_gpus": world,
-        "steps": a.steps,
-        "warmup": a.warmup,
-        "ms_per_step": ms_per_step,
-        "higher_is_better": True,
-        "scaling": "weak",
-        "vs_baseline": None,
-        "dtype": "bf16",
-        "data": "synthetic (run_speed_eval.py noise audio, random-init large-v3 weights: kwhisper.synthetic numpy recipe seed 0, the config-3 fixture's model)",
-        "config": {"workload": "config 3: whisper-large-v3 greedy generate, 30 s clips, log-mel on GPU",
-                   "model": shape.name, "global_batch": B * world, "per_gpu_batch": B,
-                   "max_length": a.max_length, "new_tokens": new_tokens, "seq_len": 1500,
-                   "parallelism": f"dp{world}"},
-        "dist": {"world": world, "rank_device": local, "device_name": torch.cuda.get_device_name(dev),
-                 "backend": dist.get_backend() if use_dist else None,
-                 "ids_gather": "all_gather of the padded int32 token matrices, inside the timed region"
-                 if use_dist else None},
         "roofline": {"kernel": cross_note,
                      "bound": "hbm", "achieved": cross_bytes / cross_t / 1e9, "peak": HBM_PEAK_GBS, "unit": "GB/s",
                      "frac": cross_bytes / cross_t / 1e9 / HBM_PEAK_GBS, "traffic": None,
@@ -459,11 +510,7 @@ def main(argv=None):
                       f"shows nproc {cb['nproc']}), a bounded sample of {a.cpu_batch} clips x 30 s (the config's 32-clip "
                       f"batch at the same thread count: profiles/r03_cpu_baseline_b32.json), "
                       f"greedy, {cb['new_tokens']} new tokens, {cb['seconds']:.1f} s; run_speed_eval.py:73-78 timing"}
-    if rank == 0:
-        print(json.dumps(result), flush=True)
-    if use_dist:
-        dist.barrier()
-        dist.destroy_process_group()
+    return result
 
 
 if __name__ == "__main__":

@@ -40,7 +40,7 @@ def gpu_available() -> bool:
 
 @pytest.fixture(scope="session")
 def gold():
-    import numpy as np
+    from oracle.fixtures import load_fixture
 
     cache = {}
 
@@ -49,7 +49,7 @@ def gold():
             path = os.path.join(GOLD, name + ".npz")
             if not os.path.exists(path):
                 pytest.skip(f"golden fixture {name} not generated")
-            cache[name] = dict(np.load(path, allow_pickle=False))
+            cache[name] = load_fixture(path)  # with the arrays kept as row blocks in <name>.part<k>.npz
         return cache[name]
 
     return load

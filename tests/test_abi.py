@@ -47,15 +47,15 @@ def test_version(lib):
     assert lib.kw_version() == want == 112
 
 
-def _c_layout(struct, fields):
+def _c_layout(struct, fields, d):
     code = "#include <stdio.h>\n#include <stddef.h>\n#include \"kwhisper.h\"\nint main(){"
     code += f'printf("%zu\\n", sizeof({struct}));'
     for f in fields:
         code += f'printf("%zu\\n", offsetof({struct}, {f}));'
     code += "return 0;}"
-    d = os.environ.get("TMPDIR", "/tmp")
-    src, exe = os.path.join(d, "kw_layout.c"), os.path.join(d, "kw_layout")
-    open(src, "w").write(code)
+    src, exe = os.path.join(d, "kw_layout.c"), os.path.join(d, "kw_layout")  # d: the test's own tmp_path
+    with open(src, "w") as f:
+        f.write(code)
     subprocess.run(["gcc", "-I", os.path.join(ROOT, "include"), src, "-o", exe], check=True)
     return [int(x) for x in subprocess.run([exe], capture_output=True, text=True, check=True).stdout.split()]
 
@@ -64,12 +64,12 @@ def _c_layout(struct, fields):
                                           ("kw_dec_linear_args", "DecLinearArgs"),
                                           ("kw_dec_qkv_self_args", "QkvSelfArgs"),
                                           ("kw_dec_xq_cross_args", "XqCrossArgs")])
-def test_struct_layout_matches_c(cname, pyname):
+def test_struct_layout_matches_c(cname, pyname, tmp_path):
     from kwhisper import _lib
 
     cls = getattr(_lib, pyname)
     fields = [f for f, _ in cls._fields_]
-    got = _c_layout(cname, fields)
+    got = _c_layout(cname, fields, str(tmp_path))
     assert got[0] == ctypes.sizeof(cls)
     for f, off in zip(fields, got[1:]):
         assert getattr(cls, f).offset == off, f

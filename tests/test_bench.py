@@ -34,6 +34,49 @@ def test_bench_single_rank_stub():
     assert r["n_gpus"] == 1 and r["dist"]["world"] == 1
 
 
+def test_bench_dump_outputs_stub(tmp_path):
+    """--dump-outputs writes what the last timed step returned as float32 .npy files, the same from run to run;
+    --steps sets the number of timed steps and the line carries ms_per_step."""
+    import numpy as np
+
+    r = _run_bench("--gpus", "1", "--stub", "--steps", "3", "--warmup", "1", "--batch", "5",
+                   "--dump-outputs", str(tmp_path / "a"))
+    assert r["steps"] == 3 and r["warmup"] == 1 and r["ms_per_step"] > 0
+    assert abs(r["value"] - 5 * 30.0 / (r["ms_per_step"] * 1e-3)) <= 1e-6 * r["value"]
+    assert sorted(os.listdir(tmp_path / "a")) == ["token_ids.npy"]
+    a = np.load(tmp_path / "a" / "token_ids.npy")
+    assert a.dtype == np.float32 and a.shape == (5, 8)
+    _run_bench("--gpus", "1", "--stub", "--steps", "3", "--warmup", "1", "--batch", "5",
+               "--dump-outputs", str(tmp_path / "b"))
+    np.testing.assert_array_equal(a, np.load(tmp_path / "b" / "token_ids.npy"))
+
+
+def test_bench_dump_outputs_per_rank_stub(tmp_path):
+    """Under --gpus 2 rank 0 writes every rank's gathered ids."""
+    import numpy as np
+
+    _run_bench("--gpus", "2", "--stub", "--steps", "1", "--warmup", "0", "--full", "--dump-outputs", str(tmp_path))
+    assert sorted(os.listdir(tmp_path)) == ["token_ids_rank0.npy", "token_ids_rank1.npy"]
+    for r in range(2):
+        a = np.load(tmp_path / f"token_ids_rank{r}.npy")
+        assert a.dtype == np.float32 and (a == r).all()
+
+
+def test_bench_extras_need_full():
+    """The measurements beside the headline value live behind --full: asking for one without it is an error, not
+    a silently leaner run."""
+    import bench
+
+    assert bench.parse(["--gpus", "1", "--steps", "2", "--warmup", "1"]).full is False
+    assert bench.parse(["--full", "--inflight", "2,3"]).inflight == "2,3"
+    try:
+        bench.parse(["--inflight", "2"])
+    except SystemExit as e:
+        assert e.code == 2
+    else:
+        raise AssertionError("--inflight without --full was accepted")
+
+
 def test_kernel_source_hash_covers_product_sources_only(tmp_path):
     sys.path.insert(0, ROOT)
     import bench

@@ -39,7 +39,7 @@ def _torchrun(script, *args, timeout=300):
 def test_bench_rank_code_over_rccl():
     """bench.py's rank code (not --stub) under the launcher: the dist path with RCCL at world size 1."""
     r = _torchrun(os.path.join(ROOT, "bench.py"), "--model", "tiny", "--batch", "4", "--steps", "1", "--warmup", "1",
-                  "--max-length", "24", "--no-cpu-baseline", "--kernel-iters", "2")
+                  "--max-length", "24", "--full", "--no-cpu-baseline", "--kernel-iters", "2")
     print("\nbench over RCCL:", json.dumps({k: r[k] for k in ("value", "n_gpus", "dist")}))
     assert r["n_gpus"] == 1 and r["dist"]["backend"] == "nccl" and r["dist"]["ids_gather"]
     assert r["value"] > 0

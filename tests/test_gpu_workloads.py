@@ -565,7 +565,9 @@ def _c4_worker(rank, world, port, out_dir, batch_size, name):
 
     dist.init_process_group("gloo", init_method=f"tcp://127.0.0.1:{port}", rank=rank, world_size=world)
     try:
-        g = dict(np.load(os.path.join(os.path.dirname(__file__), "golden", f"{name}.npz")))
+        from oracle.fixtures import load_fixture
+
+        g = load_fixture(os.path.join(os.path.dirname(__file__), "golden", f"{name}.npz"))
         model = _model(LARGE_V3, torch.bfloat16)
         feats = _c4_features(g)
         ids, preds = _c4_pseudo_label(model, g["durations"], feats, batch_size)

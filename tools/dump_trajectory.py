@@ -34,7 +34,10 @@ def main():
     from kwhisper.generation import KWhisperForConditionalGeneration
     from kwhisper.synthetic import synthetic_state_dict
 
-    g = np.load(a.fixture)
+    sys.path.insert(0, ROOT)
+    from oracle.fixtures import load_fixture
+
+    g = load_fixture(a.fixture)  # the features are stored as row blocks beside it
     feats = torch.from_numpy(g["features"]).cuda()
     kw = dict(language="ja", task="transcribe", return_timestamps=True, max_length=int(g["max_length"]))
     out = {}

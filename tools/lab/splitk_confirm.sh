@@ -15,5 +15,5 @@ done
 for cfg in default 10,6 default 10,6; do
   if [ "$cfg" = default ]; then unset KW_DECLIN_GEO; else export KW_DECLIN_GEO=1280,5120,1,$cfg; fi
   echo -n "bench $cfg "
-  timeout -k 10 300 python bench.py --no-cpu-baseline --steps 4 2>/dev/null | python -c "import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print(round(d['value'],1),round(d['decode_step_ms'],4))" || exit 1
+  timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 4 2>/dev/null | python -c "import json,sys;d=json.loads(sys.stdin.read().strip().splitlines()[-1]);print(round(d['value'],1),round(d['decode_step_ms'],4))" || exit 1
 done

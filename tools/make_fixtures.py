@@ -451,8 +451,11 @@ def large_config4_hipmel_fixtures(features_npz, bf16=True, seed=0, name="large_v
         out["bf16_passes"] = np.bincount([r for it in r16.iters for r in it["rows"]], minlength=feats.shape[0])
         print(f"  {name}: bf16 generate ({time.time() - t0:.1f}s), passes {out['bf16_passes'].tolist()}")
     out["seed"] = np.int64(seed)
-    np.savez_compressed(os.path.join(GOLD, f"{name}.npz"), **out)
-    print(f"{name} fixtures done in {time.time() - t0:.1f}s {toks.shape}")
+    sys.path.insert(0, ROOT)
+    from oracle.fixtures import save_fixture
+
+    files = save_fixture(os.path.join(GOLD, f"{name}.npz"), out)  # the features as row blocks, each file < 1 MiB
+    print(f"{name} fixtures done in {time.time() - t0:.1f}s {toks.shape}, {len(files)} files")
 
 
 def large_config4_traj_fixtures(traj_npz):
@@ -466,10 +469,11 @@ def large_config4_traj_fixtures(traj_npz):
     WhisperTimeStamp, pinned to transformers by tests/test_oracle_golden.py) and reduced to fp32's choice and its
     top-1 / top-2 margin at every step of the engine's trajectory."""
     sys.path.insert(0, ROOT)
+    from oracle.fixtures import load_fixture
     from oracle.generate import process_logits
 
     t0 = time.time()
-    g = np.load(os.path.join(GOLD, "large_v3_c4_hipmel.npz"))
+    g = load_fixture(os.path.join(GOLD, "large_v3_c4_hipmel.npz"))
     tr = np.load(traj_npz)
     feats = torch.from_numpy(g["features"].astype(np.float32))
     m = hf_model(LARGE_V3)
