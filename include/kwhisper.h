@@ -96,16 +96,32 @@ int kw_gemm(const kw_gemm_args* args, kw_stream_t stream);
  *          bf16 mirror the next LayerNorm-fused linear reads.
  * W: packed by kw_pack_weight.  workspace: >= kw_dec_linear_workspace_bytes(N, K) bytes, zero-filled
  * before first use (calls leave it zeroed); one workspace may serve all calls on one stream.
- * Results are bitwise deterministic (fixed-order reductions, no float atomics). */
+ * Results are bitwise deterministic (fixed-order reductions, no float atomics).
+ *
+ * Fragment-major activations: ldx == KW_LD_TILED says x is stored in the order the matrix cores take it
+ * (the A operand of v_mfma_f32_16x16x32_bf16), for M <= 32 rows in T = ceil(M / 16) row tiles: element (m, k)
+ * is element k % 8 of 16-B piece ((k / 32) * T + m / 16) * 64 + m % 16 + 16 * ((k % 32) / 8), the buffer holding
+ * (K / 32) * T * 1 KB.  Rows M .. 16 T - 1 may hold anything (they feed discarded outputs only).  Same results,
+ * bit for bit; a wave's load of one (k-tile, row tile) is one contiguous 1-KB access.  Read by kw_dec_linear
+ * (M <= 32; LM head shapes: those its persistent kernel covers, kw_dec_lm_greedy_supported), kw_dec_lm_greedy,
+ * kw_dec_qkv_self and kw_dec_xq_cross (a block called with ldx == KW_LD_TILED also WRITES its out [M][d] in this
+ * order, for the o / xo linear that follows); any other use returns KW_EINVAL.
+ * Written by the producers of the bf16 residual mirror: kw_dec_linear's RESID epilogue with
+ * epilogue = KW_EPI_RESID | KW_EPI_HB_TILED (hb fragment-major over ceil(M / 16) row tiles, M <= 32, N % 32 == 0;
+ * h stays [M][ldh] f32) and kw_embed with dtype | KW_EMBED_HB_TILED (q_len 1, B <= 32, bf16 tables, d % 32 == 0).
+ * Rows >= M of the buffer are never written. */
+#define KW_LD_TILED ((int64_t)-1)
+#define KW_EPI_HB_TILED 0x100
+#define KW_EMBED_HB_TILED 0x100
 typedef struct {
   const void* x;
-  int64_t ldx;
+  int64_t ldx;               /* row stride in elements, or KW_LD_TILED */
   int ln;                    /* fuse the LayerNorm of x (STORE only) */
   float ln_eps;
   const float* ln_colsum;    /* [N], required with ln */
   const void* W;
   const float* bias;         /* [N] f32 or NULL */
-  int epilogue;              /* KW_EPI_STORE or KW_EPI_RESID */
+  int epilogue;              /* KW_EPI_STORE or KW_EPI_RESID (| KW_EPI_HB_TILED) */
   void* C;                   /* STORE output [M][ldc] */
   int64_t ldc;
   int c_dtype;
@@ -148,7 +164,8 @@ int kw_attention(int dtype, const void* qkv, int64_t B, int64_t H, int64_t T, in
 
 /* Decoder input embedding: h[b*q_len+i] = tok_emb[ids[b][L-q_len+i]] + pos_emb[L-q_len+i]
  * with L = *cur_len read on device (TF modeling_whisper.py:737-762; no embed scale); hb (optional,
- * bf16, may be NULL) receives bf16(h) for the bf16 engine's LayerNorm-fused linears. */
+ * bf16, may be NULL) receives bf16(h) for the bf16 engine's LayerNorm-fused linears -- fragment-major with
+ * dtype | KW_EMBED_HB_TILED (see kw_dec_linear). */
 int kw_embed(int dtype, const int64_t* ids, int64_t ids_stride, int64_t B, int64_t q_len,
              const int32_t* cur_len, const void* tok_emb, const void* pos_emb, int64_t d, float* h,
              void* hb, kw_stream_t stream);

@@ -803,7 +803,7 @@ __device__ __forceinline__ void publish_and_combine(float* part, int* cnt, int n
 // expected) raises the error word and writes NaN, so the failure is loud.
 __device__ __forceinline__ void wave_partials_combine(unsigned long long* gr, int ns, int split, float mw, float lw,
                                                       const float (&acc)[8], float (*red)[64], float* stat,
-                                                      bf16_t* out_row, int* err) {
+                                                      bf16_t* out_el, int* err) {  // out_el: lane's element (dim tid & 63)
   constexpr int G = HD + 2, NSMAX = 8;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   if (lane < 8) {  // the wave's partial of dim d = lane*8 + i, read back by lane d of the same wave (in order)
@@ -880,7 +880,7 @@ __device__ __forceinline__ void wave_partials_combine(unsigned long long* gr, in
   if (tid < HD) {
     float m, l, o;
     merge_waves_bf16(stat, red, tid, m, l, o);
-    TypeIO<bf16_t>::st(out_row + tid, o / l);
+    TypeIO<bf16_t>::st(out_el, o / l);
   }
 }
 
@@ -1040,7 +1040,7 @@ __global__ __launch_bounds__(256) void cross_attn_dma_kernel(const bf16_t* __res
   float mw, lw, acc[8];
   wave_row_bf16(ql, kr, vr, k0, k1, slot, 8, mw, lw, acc);
   wave_partials_combine(gran + (int64_t)row * ns * 4 * (HD + 2), ns, split, mw, lw, acc, red, stat,
-                        out + (int64_t)bq * H * HD + h * HD, err);
+                        out + (int64_t)bq * H * HD + h * HD + (threadIdx.x & 63), err);
 }
 
 // ------------------------------------------------------------------------------------------------
@@ -1077,6 +1077,7 @@ struct XQP {
   unsigned long long* gran;  // cross_attn_dma_kernel's chunk-partial granules
   int* err;
   bf16_t* out;
+  int out_t;  // out fragment-major over out_t row tiles (a KW_LD_TILED call: x and out); 0: [M][d]
 };
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void xq_cross_kernel(XQP p) {
@@ -1144,7 +1145,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void x
   float mw, lw, acc[8];
   wave_row_bf16(ql, kr, vr, k0, k1, slot, 8, mw, lw, acc);
   wave_partials_combine(p.gran + (int64_t)row * ns * 4 * (HD + 2), ns, split, mw, lw, acc, red, stat,
-                        p.out + (int64_t)b * p.d + h * HD, p.err);
+                        p.out + (p.out_t ? kw_tiled_off(b, h * HD + (tid & 63), p.out_t) : (int64_t)b * p.d + h * HD + (tid & 63)), p.err);
   if (split == ns - 1 && tid < 32)  // re-arm the row's query for the next launch (every chunk has read it)
     __hip_atomic_store(qg + tid, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -1167,6 +1168,7 @@ struct CRP {
   int H, d, S, chunk, ns, n_lin;
   int* err;
   bf16_t* out;
+  int out_t;  // out fragment-major over out_t row tiles (kw_dec_xq_cross with KW_LD_TILED); 0: row stride d
   ProjArgs proj;  // QG: the query projection
 };
 
@@ -1295,7 +1297,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
   __syncthreads();
   float m, l, o;
   merge_waves_bf16(stat, red, tid, m, l, o);
-  if (tid < HD) TypeIO<bf16_t>::st(p.out + (int64_t)b * p.d + h * HD + tid, o / l);
+  if (tid < HD) TypeIO<bf16_t>::st(p.out + (p.out_t ? kw_tiled_off(b, h * HD + tid, p.out_t) : (int64_t)b * p.d + h * HD + tid), o / l);
   if constexpr (QG) {
     if (tid < 32)  // re-arm the row's query for the next launch (every wave of this, its only reader, has read it)
       __hip_atomic_store(qg + tid, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1929,7 +1931,7 @@ extern "C" int kw_dec_xq_cross_supported(int64_t M, int64_t d, int64_t H, int64_
 extern "C" int kw_dec_xq_cross(const kw_dec_xq_cross_args* a, kw_stream_t stream) {
   if (!a || !a->x || !a->W || !a->ln_colsum || !a->k || !a->v || !a->out || !a->workspace)
     return kw_set_error_msg(KW_EINVAL, "kw_dec_xq_cross: null pointer");
-  if (!xq_shape_ok(a->M, a->d, a->H, a->S) || a->ldx < a->d || a->ldx % 8 || (uintptr_t)a->x % 16)
+  if (!xq_shape_ok(a->M, a->d, a->H, a->S) || (a->ldx != KW_LD_TILED && (a->ldx < a->d || a->ldx % 8)) || (uintptr_t)a->x % 16)
     return kw_set_error_msg(KW_EINVAL, "kw_dec_xq_cross: M <= 32 rows, d = 64 H <= 1280, 224 < S / chunks <= 256, "
                                        "ldx % 8 == 0, 16-B aligned x");
   if (a->ws_bytes < kw_dec_xq_cross_workspace(a->M, a->d, a->H, a->S))
@@ -1956,6 +1958,7 @@ extern "C" int kw_dec_xq_cross(const kw_dec_xq_cross_args* a, kw_stream_t stream
   p.gran = reinterpret_cast<unsigned long long*>(ws + cross_granule_offset(a->M, 1, a->H, a->S));
   p.err = reinterpret_cast<int*>(ws + cross_partials_bytes(a->M, 1, a->H, a->S)) + a->M * a->H;
   p.out = reinterpret_cast<bf16_t*>(a->out);
+  p.out_t = a->ldx == KW_LD_TILED ? (int)((a->M + 15) / 16) : 0;
   if (row_kernel_fits<true>(a->M * a->H, a->S)) {  // one pair workgroup per (row, head), chunks pipelined
     CRP r{};
     r.qg = p.qg;
@@ -1964,6 +1967,7 @@ extern "C" int kw_dec_xq_cross(const kw_dec_xq_cross_args* a, kw_stream_t stream
     r.H = p.H, r.d = p.d, r.S = p.S, r.chunk = p.chunk, r.ns = p.ns, r.n_lin = p.n_lin;
     r.err = p.err;
     r.out = p.out;
+    r.out_t = p.out_t;
     r.proj = ProjArgs{p.x, p.ldx, p.M, p.d, p.d, p.ln_eps, p.ln_colsum, p.W, p.bias, p.scale, p.d, p.err + 1};
     hipLaunchKernelGGL((cross_attn_row_kernel<true, ROW_NS>), dim3((unsigned)(p.n_lin + a->M * a->H)), dim3(256), 0,
                        (hipStream_t)stream, r);

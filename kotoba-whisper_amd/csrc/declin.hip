@@ -70,14 +70,22 @@ struct DecP {
   int xlds;  // stage the activation rows through LDS (single-round grids and split-K slices)
   int zrows; // rows per grid z-chunk: 32, or 16 for narrow grids (row split, launch())
   int vec_epi;  // outputs in whole 16-B pieces (N % 16 == 0, 16-B aligned rows): the epilogue stores 16-B pieces
+  int xt;       // x is fragment-major (KW_LD_TILED: [k-tile][row tile][64 lanes][8]) with xt row tiles; 0: row-major
+  int hbt;      // RESID: hb is written fragment-major (KW_EPI_HB_TILED) with hbt row tiles; 0: row-major [M][ldh]
 };
+
+// hb's element (m, n): the bf16 residual mirror, row-major or fragment-major
+__device__ __forceinline__ bf16_t* hb_at(const DecP& p, int m, int n) {
+  return p.hb + (p.hbt ? kw_tiled_off(m, n, p.hbt) : (int64_t)m * p.ldh + n);
+}
 
 // One wave's 16 x 16 output block: lane holds rows mb + 4 (lane / 16) + r (r < 4) of column nb + lane % 16 (the MFMA C
 // layout).  vec (DecP::vec_epi): staged row-major in stg (the wave's own 16 x 20 floats of LDS) and stored as whole
 // 16-B pieces -- f32 rows of 4 columns (one per lane), bf16 rows of 8 (lanes 0..31) -- otherwise element by element;
 // rows >= M and columns >= N are not stored.  RESID: h (f32) and its bf16 mirror hb; STORE: C of TC.  r06: the
 // element stores wrote 16 columns x 4 rows of 2-4-B pieces per instruction.
-template <int EPI, typename TC>
+// TH: hb may be fragment-major (p.hbt; dec_linear_kernel only -- the rows kernel's stores stay as they were)
+template <int EPI, typename TC, bool TH = false>
 __device__ __forceinline__ void store_block16(const DecP& p, float (*stg)[20], const float (&v4)[4], int mb, int M,
                                               int nb, int lane) {
   if (p.vec_epi) {
@@ -101,7 +109,8 @@ __device__ __forceinline__ void store_block16(const DecP& p, float (*stg)[20], c
       if (lane < 32 && m < M && nb + 8 * q < p.N) {
         const f32x4 a = *reinterpret_cast<const f32x4*>(&stg[ml][8 * q]);
         const f32x4 b = *reinterpret_cast<const f32x4*>(&stg[ml][8 * q + 4]);
-        *reinterpret_cast<u32x4*>(dst + (int64_t)m * ld + nb + 8 * q) =
+        // (a fragment-major hb: the block's 16 rows x 8 columns are one contiguous 256-B run per q)
+        *reinterpret_cast<u32x4*>(TH && EPI == KW_EPI_RESID ? hb_at(p, m, nb + 8 * q) : dst + (int64_t)m * ld + nb + 8 * q) =
             u32x4{pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(b[0], b[1]), pack_bf16x2(b[2], b[3])};
       }
     }
@@ -113,7 +122,7 @@ __device__ __forceinline__ void store_block16(const DecP& p, float (*stg)[20], c
       if (n >= p.N || m >= M) continue;
       if constexpr (EPI == KW_EPI_RESID) {
         p.h[(int64_t)m * p.ldh + n] = v4[r];
-        p.hb[(int64_t)m * p.ldh + n] = f2bf(v4[r]);
+        *(TH ? hb_at(p, m, n) : p.hb + (int64_t)m * p.ldh + n) = f2bf(v4[r]);
       } else {
         TypeIO<TC>::st(reinterpret_cast<TC*>(p.C) + (int64_t)m * p.ldc + n, v4[r]);
       }
@@ -158,7 +167,19 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
   const int wkt0 = (nkt * ks) / ksn, wkt1 = (nkt * (ks + 1)) / ksn;  // this workgroup's k-tiles
   const int cpr = (wkt1 - wkt0) * 4, cprp = cpr + 1;
   const bool xlds = p.xlds;
-  if (xlds) {
+  // fragment-major x (p.xt row tiles): a (k-tile, row half) fragment is one contiguous 1-KB piece, loaded straight
+  // into registers with the weights -- no LDS image, no barrier, no row clamp (a missing second tile re-reads the
+  // first: its output rows are >= M)
+  if (p.xt) {
+    const bf16x8* xf = reinterpret_cast<const bf16x8*>(p.x) + lane;
+    const int t1 = p.xt > 1 ? 64 : 0;
+#pragma unroll
+    for (int u = 0; u < KTM; ++u) {
+      const bf16x8* f = xf + (int64_t)(min(kt0 + u, ktl) * p.xt) * 64;
+      a0[u] = *f;
+      if constexpr (H2) a1[u] = f[t1];
+    }
+  } else if (xlds) {
     // <= 16 rows: only the pieces of rows 0..15 (the second row half's fragments then hold stale LDS, and its
     // output rows -- all >= M -- are discarded; every row of an MFMA tile is independent of the others)
     const int ninst = ((M <= 16 ? 16 : 32) * cprp + 63) / 64;
@@ -205,7 +226,8 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
     }
   }
 
-  if (xlds) {
+  if (p.xt) {  // (fragments already in flight)
+  } else if (xlds) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
 #pragma unroll
@@ -340,7 +362,7 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
       }
       v4[r] = v;
     }
-    store_block16<EPI, TC>(p, stg[wave], v4, 16 * hj, M, nb, lane);
+    store_block16<EPI, TC, true>(p, stg[wave], v4, 16 * hj, M, nb, lane);
     KW_DEC_STAMP(4);
     KW_DEC_STAMP_FLUSH
     return;
@@ -482,7 +504,7 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
         if (pc < R * NCB * 2 && m < M && n0 + 8 * q < p.N) {
           const f32x4 a = *reinterpret_cast<const f32x4*>(stg + m * SW + 8 * q);
           const f32x4 b = *reinterpret_cast<const f32x4*>(stg + m * SW + 8 * q + 4);
-          *reinterpret_cast<u32x4*>(dst + (int64_t)m * ld + n0 + 8 * q) =
+          *reinterpret_cast<u32x4*>(EPI == KW_EPI_RESID ? hb_at(p, m, n0 + 8 * q) : dst + (int64_t)m * ld + n0 + 8 * q) =
               u32x4{pack_bf16x2(a[0], a[1]), pack_bf16x2(a[2], a[3]), pack_bf16x2(b[0], b[1]), pack_bf16x2(b[2], b[3])};
         }
       }
@@ -500,7 +522,7 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
           const float v = vals[c][hh][r];
           if constexpr (EPI == KW_EPI_RESID) {
             p.h[(int64_t)m * p.ldh + n] = v;
-            p.hb[(int64_t)m * p.ldh + n] = f2bf(v);
+            *hb_at(p, m, n) = f2bf(v);
           } else {
             TypeIO<TC>::st(reinterpret_cast<TC*>(p.C) + (int64_t)m * p.ldc + n, v);
           }
@@ -523,10 +545,10 @@ __global__ __launch_bounds__(512) void dec_linear_kernel(DecP p0, int ksn) {
   if (blockIdx.z) {
     const int m0 = p0.zrows * blockIdx.z;
     p.M = min(p0.zrows, p0.M - m0);
-    p.x += m0 * p0.ldx;
+    p.x += p0.xt ? m0 * 32 : m0 * p0.ldx;  // (fragment-major: 16-row chunks only -- the next row tile, 512 elements on)
     if (p.C) p.C = reinterpret_cast<char*>(p.C) + (int64_t)m0 * p0.ldc * (sizeof(TC));
     if (p.h) p.h += m0 * p0.ldh;
-    if (p.hb) p.hb += m0 * p0.ldh;
+    if (p.hb) p.hb += p0.hbt ? m0 * 32 : m0 * p0.ldh;  // (fragment-major: the next row tile, as x)
   } else {
     p.M = min(p0.zrows, p0.M);
   }
@@ -1112,7 +1134,16 @@ __global__ __launch_bounds__(512) void lm_head_kernel(DecP p0, int groups_per_wg
   }
   // activation fragments of this wave's k-range, once (rows lane&15 and 16 + lane&15)
   bf16x8 a0[LMH_KTM], a1[LMH_KTM];
-  {
+  if (p.xt) {  // fragment-major x (M <= 32, one z-chunk): each fragment one contiguous 1-KB piece, as dec_linear_body
+    const bf16x8* xf = reinterpret_cast<const bf16x8*>(p.x) + lane;
+    const int t1 = p.xt > 1 ? 64 : 0;
+#pragma unroll
+    for (int u = 0; u < LMH_KTM; ++u) {
+      const bf16x8* f = xf + (int64_t)(min(kt0 + u, ktl) * p.xt) * 64;
+      a0[u] = *f;
+      a1[u] = f[t1];
+    }
+  } else {
     const int r0 = min(lane & 15, M - 1), r1 = min(16 + (lane & 15), M - 1), akoff = 8 * (lane >> 4);
 #pragma unroll
     for (int u = 0; u < LMH_KTM; ++u) {
@@ -1421,8 +1452,8 @@ extern "C" int kw_dec_lm_greedy_supported(int64_t B, int64_t V, int64_t d) {
 }
 
 extern "C" int kw_dec_lm_greedy(const kw_dec_linear_args* a, const kw_sampler_args* g, kw_stream_t stream) {
-  if (!a || !g || !a->x || !a->W || !a->ln || !a->ln_colsum || a->K <= 0 || a->K % 32 != 0 || a->ldx % 8 != 0 ||
-      a->ldx < a->K || (uintptr_t)a->x % 16 != 0 || a->epilogue != KW_EPI_STORE || a->gelu || a->scale_cols != 0 ||
+  if (!a || !g || !a->x || !a->W || !a->ln || !a->ln_colsum || a->K <= 0 || a->K % 32 != 0 ||
+      (a->ldx != KW_LD_TILED && (a->ldx % 8 != 0 || a->ldx < a->K)) || (uintptr_t)a->x % 16 != 0 || a->epilogue != KW_EPI_STORE || a->gelu || a->scale_cols != 0 ||
       (a->C && (a->c_dtype != KW_DT_F32 || a->ldc < a->N)))
     return kw_set_error_msg(KW_EINVAL, "kw_dec_lm_greedy: the LM head must be LayerNorm-fused STORE into f32 (or no) logits");
   if (!g->suppress_mask || !g->ids || !g->cur_len || !g->unfinished || !g->n_unfinished || !g->workspace ||
@@ -1447,6 +1478,7 @@ extern "C" int kw_dec_lm_greedy(const kw_dec_linear_args* a, const kw_sampler_ar
   p.M = (int)a->M;
   p.N = (int)a->N;
   p.K = (int)a->K;
+  p.xt = a->ldx == KW_LD_TILED ? (int)((a->M + 15) / 16) : 0;  // (M <= 32: kw_dec_lm_greedy_supported)
   LmGreedy sg{};
   sg.mask = g->suppress_mask;
   sg.bsup = g->begin_suppress;
@@ -1477,19 +1509,24 @@ extern "C" size_t kw_dec_linear_workspace_bytes(int64_t N, int64_t K) {
 }
 
 extern "C" int kw_dec_linear(const kw_dec_linear_args* a, kw_stream_t stream) {
-  if (!a || !a->x || !a->W || a->M < 0 || a->N <= 0 || a->K <= 0 || a->K % 32 != 0 || a->ldx % 8 != 0 || a->ldx < a->K ||
-      (uintptr_t)a->x % 16 != 0)
+  const bool xtiled = a && a->ldx == KW_LD_TILED;  // x fragment-major (include/kwhisper.h)
+  if (!a || !a->x || !a->W || a->M < 0 || a->N <= 0 || a->K <= 0 || a->K % 32 != 0 ||
+      (!xtiled && (a->ldx % 8 != 0 || a->ldx < a->K)) || (uintptr_t)a->x % 16 != 0)
     return kw_set_error_msg(KW_EINVAL, "kw_dec_linear: null pointer or bad sizes (K % 32 == 0, ldx % 8 == 0, x 16-B aligned)");
-  if (a->epilogue == KW_EPI_RESID) {
+  const int epi = a->epilogue & ~KW_EPI_HB_TILED;
+  const bool hbtiled = (a->epilogue & KW_EPI_HB_TILED) != 0;  // RESID: hb written fragment-major
+  if (hbtiled && (epi != KW_EPI_RESID || a->M > 32 || a->N % 32 != 0))
+    return kw_set_error_msg(KW_EINVAL, "kw_dec_linear: KW_EPI_HB_TILED needs the RESID epilogue, M <= 32 and N % 32 == 0");
+  if (epi == KW_EPI_RESID) {
     if (!a->h || !a->hb || a->ldh < a->N)
       return kw_set_error_msg(KW_EINVAL, "kw_dec_linear: RESID needs h (f32) and hb (bf16) with ldh >= N");
-  } else if (a->epilogue == KW_EPI_STORE) {
+  } else if (epi == KW_EPI_STORE) {
     if (!a->C || a->ldc < a->N || (a->c_dtype != KW_DT_F32 && a->c_dtype != KW_DT_BF16))
       return kw_set_error_msg(KW_EINVAL, "kw_dec_linear: STORE needs C (f32 or bf16) with ldc >= N");
   } else {
     return kw_set_error_msg(KW_EINVAL, "kw_dec_linear: epilogue must be STORE or RESID");
   }
-  if (a->ln && (!a->ln_colsum || a->epilogue != KW_EPI_STORE))
+  if (a->ln && (!a->ln_colsum || epi != KW_EPI_STORE))
     return kw_set_error_msg(KW_EINVAL, "kw_dec_linear: fused LayerNorm needs ln_colsum and the STORE epilogue");
   if (a->M == 0) return KW_OK;
   const Geo g = choose(a->N, a->K);
@@ -1505,8 +1542,11 @@ extern "C" int kw_dec_linear(const kw_dec_linear_args* a, kw_stream_t stream) {
   hipStream_t s = (hipStream_t)stream;
   // LM head: LayerNorm-fused, f32 logits, a wide N and a short K -> the persistent weight stream up to
   // 32 rows, the all-rows GEMM up to LMR_MAXROWS (beam rows), the weight-stationary rows kernel beyond
-  const bool lm_shape = a->ln && a->epilogue == KW_EPI_STORE && a->c_dtype == KW_DT_F32 && a->N >= 8192 && !a->gelu &&
+  const bool lm_shape = a->ln && epi == KW_EPI_STORE && a->c_dtype == KW_DT_F32 && a->N >= 8192 && !a->gelu &&
                         a->scale_cols == 0;
+  // a fragment-major x is read by dec_linear_kernel and the persistent LM head: <= 32 rows (one or two row tiles)
+  if (xtiled && (a->M > 32 || (lm_shape && !lmh_fits(a->M, a->N, nkt))))
+    return kw_set_error_msg(KW_EINVAL, "kw_dec_linear: a KW_LD_TILED x needs M <= 32 (LM head: a shape lm_head_kernel covers)");
   if (lm_shape && a->M > LMH_MAX_ROWS && a->M <= LMR_MAXROWS && nkt % 8 == 0) {
     DecP p{};
     p.x = reinterpret_cast<const bf16_t*>(a->x);
@@ -1559,10 +1599,12 @@ extern "C" int kw_dec_linear(const kw_dec_linear_args* a, kw_stream_t stream) {
     p.ldh = a->ldh;
     p.cnt = reinterpret_cast<int*>(a->workspace);
     p.slab = a->workspace ? reinterpret_cast<float*>(reinterpret_cast<char*>(a->workspace) + CNT_MAX * sizeof(int)) : nullptr;
-    p.xlds = use_xlds(a->N, g) ? 1 : 0;
+    p.xt = xtiled ? (int)((a->M + 15) / 16) : 0;
+    p.hbt = hbtiled ? (int)((a->M + 15) / 16) : 0;
+    p.xlds = !xtiled && use_xlds(a->N, g) ? 1 : 0;
     // 16-B epilogue pieces: whole 16-column blocks and 16-B aligned rows (every z-chunk's rows too)
     p.vec_epi = a->N % 16 == 0 &&
-                (a->epilogue == KW_EPI_RESID
+                (epi == KW_EPI_RESID
                      ? a->ldh % 8 == 0 && (uintptr_t)p.h % 16 == 0 && (uintptr_t)p.hb % 16 == 0
                      : (a->ldc * (int64_t)csz) % 16 == 0 && (uintptr_t)p.C % 16 == 0);
     if (lmh) {
@@ -1575,7 +1617,7 @@ extern "C" int kw_dec_linear(const kw_dec_linear_args* a, kw_stream_t stream) {
       if (e != hipSuccess) return kw_set_error(e);
       continue;
     }
-    hipError_t e = launch(p, a->epilogue == KW_EPI_RESID, g, a->c_dtype == KW_DT_F32, s);
+    hipError_t e = launch(p, epi == KW_EPI_RESID, g, a->c_dtype == KW_DT_F32, s);
     if (e != hipSuccess) return kw_set_error(e);
   }
   return KW_OK;

@@ -6,7 +6,8 @@
 // Bitwise dec_linear's values: its 8-wave geometry (nv = ceil(nkt / 5) waves of 5 k-tiles, wave v owning
 // k-tiles [nkt v / nv, nkt (v + 1) / nv)) runs as VIRTUAL waves v = wave + 4 r (r = 0, 1) -- the same
 // fragments and MFMA order per v -- and the partial tiles and LayerNorm row sums are reduced in v order
-// through LDS, as the launch reduces its waves.  A fragments come straight from the activation rows (L2).
+// through LDS, as the launch reduces its waves.  A fragments come straight from the activation rows (L2), or from a
+// fragment-major copy of them (KW_LD_TILED).
 #pragma once
 #include "kw_common.h"
 
@@ -22,8 +23,8 @@ constexpr int PROJ_NV = 8;                       // virtual waves: K <= 8 x 5 x 
 constexpr int PROJ_SCRATCH = 16384 + 2048 + 256;  // LDS: partial tiles [8][2][64] f32x4, row sums [8][32][2], stats
 
 struct ProjArgs {
-  const bf16_t* x;  // [M][ldx] bf16 (the LayerNorm's input rows)
-  int64_t ldx;
+  const bf16_t* x;  // [M][ldx] bf16 (the LayerNorm's input rows); ldx == KW_LD_TILED: fragment-major
+  int64_t ldx;      //   [k-tile][row tile][64 lanes][8], a (k-tile, row half) fragment one contiguous 1-KB piece
   int M, K, N;
   float ln_eps;
   const float* colsum;  // [N] column sums of the gamma-folded weight
@@ -53,8 +54,12 @@ __device__ __forceinline__ void proj_publish_granules(const ProjArgs& a, int cg,
   const int M = a.M, nkt = a.K >> 5;
   const int nv = (nkt + PROJ_KTM - 1) / PROJ_KTM;
   KW_PROJ_STAMP(0);
-  const bf16_t* x0 = a.x + (int64_t)min(lane & 15, M - 1) * a.ldx + (lane >> 4) * 8;
-  const bf16_t* x1 = a.x + (int64_t)min(16 + (lane & 15), M - 1) * a.ldx + (lane >> 4) * 8;
+  // fragment-major x: lane's 16 B of k-tile kt at kt * xks (a missing second row tile re-reads the first: its output
+  // rows are >= M); row-major: rows clamped to M - 1
+  const bool xtiled = a.ldx == KW_LD_TILED;
+  const int xks = xtiled ? (M > 16 ? 1024 : 512) : 32;
+  const bf16_t* x0 = xtiled ? a.x + lane * 8 : a.x + (int64_t)min(lane & 15, M - 1) * a.ldx + (lane >> 4) * 8;
+  const bf16_t* x1 = xtiled ? x0 + (M > 16 ? 512 : 0) : a.x + (int64_t)min(16 + (lane & 15), M - 1) * a.ldx + (lane >> 4) * 8;
   const int n_e = min(cg * 16 + (lane & 15), a.N - 1);
   const float ebias = a.bias ? a.bias[n_e] : 0.f;
   const float ecsum = a.colsum[n_e];
@@ -85,8 +90,8 @@ __device__ __forceinline__ void proj_publish_granules(const ProjArgs& a, int cg,
 #pragma unroll
     for (int u = 0; u < PROJ_KTM; ++u) {
       const int kt = min(kt0 + u, ktl);
-      av[r][0][u] = *reinterpret_cast<const bf16x8*>(x0 + kt * 32);
-      av[r][1][u] = *reinterpret_cast<const bf16x8*>(x1 + kt * 32);
+      av[r][0][u] = *reinterpret_cast<const bf16x8*>(x0 + kt * xks);
+      av[r][1][u] = *reinterpret_cast<const bf16x8*>(x1 + kt * xks);
     }
   };
   load_a(0);

@@ -35,6 +35,12 @@ __device__ __forceinline__ uint32_t pack_bf16x2(float lo, float hi) {
   return __builtin_bit_cast(uint32_t, v);
 }
 
+// Element offset of (row m, column n) in a fragment-major bf16 activation buffer of T row tiles (KW_LD_TILED,
+// include/kwhisper.h): [k-tile][row tile][64 lanes][8] -- 8 consecutive columns of a row stay one 16-B piece
+__device__ __forceinline__ int64_t kw_tiled_off(int m, int n, int T) {
+  return ((int64_t)((n >> 5) * T + (m >> 4)) * 64 + (m & 15) + 16 * ((n & 31) >> 3)) * 8 + (n & 7);
+}
+
 template <typename T> struct TypeIO;
 template <> struct TypeIO<float> {
   static __device__ __forceinline__ float ld(const float* p) { return *p; }

@@ -194,7 +194,9 @@ __global__ __launch_bounds__(256) void mel_tm_kernel(const float* __restrict__ m
 __global__ __launch_bounds__(256) void embed_bf16x8_kernel(const int64_t* __restrict__ ids, int64_t ids_stride, int q_len,
                                                            const int32_t* __restrict__ cur_len, const bf16_t* __restrict__ tok,
                                                            const bf16_t* __restrict__ pos, int d, float* __restrict__ h,
-                                                           bf16_t* __restrict__ hb) {
+                                                           bf16_t* __restrict__ hb, int hbt) {
+  // hbt: hb fragment-major over hbt row tiles (KW_EMBED_HB_TILED; q_len 1) -- row r's 16-B piece of columns c..c+7
+  // is piece ((c / 32) hbt + r / 16) 64 + r % 16 + 16 ((c % 32) / 8); 0: row-major
   const int r = blockIdx.x;  // b*q_len + i
   const int b = r / q_len, i = r - b * q_len;
   const int p = *cur_len - q_len + i;
@@ -212,7 +214,8 @@ __global__ __launch_bounds__(256) void embed_bf16x8_kernel(const int64_t* __rest
     *reinterpret_cast<f32x4*>(hr) = f32x4{v[0], v[1], v[2], v[3]};
     *reinterpret_cast<f32x4*>(hr + 4) = f32x4{v[4], v[5], v[6], v[7]};
     if (hb)
-      *reinterpret_cast<u32x4*>(hb + (int64_t)r * d + c) =
+      *reinterpret_cast<u32x4*>(hbt ? hb + ((int64_t)((c >> 5) * hbt + (r >> 4)) * 64 + (r & 15) + 16 * ((c & 31) >> 3)) * 8
+                                    : hb + (int64_t)r * d + c) =
           u32x4{pack_bf16x2(v[0], v[1]), pack_bf16x2(v[2], v[3]), pack_bf16x2(v[4], v[5]), pack_bf16x2(v[6], v[7])};
   }
 }
@@ -287,17 +290,23 @@ extern "C" int kw_mel_to_time_major(const float* mel, int64_t B, int64_t C, int6
 extern "C" int kw_embed(int dtype, const int64_t* ids, int64_t ids_stride, int64_t B, int64_t q_len,
                         const int32_t* cur_len, const void* tok_emb, const void* pos_emb, int64_t d, float* h,
                         void* hb, kw_stream_t stream) {
+  const bool hbtiled = (dtype & KW_EMBED_HB_TILED) != 0;
+  dtype &= ~KW_EMBED_HB_TILED;
   if (!ids || !cur_len || !tok_emb || !pos_emb || !h || B <= 0 || q_len <= 0 || d <= 0)
     return kw_set_error_msg(KW_EINVAL, "kw_embed: invalid arguments");
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)(B * q_len));
   const bool vec = dtype == KW_DT_BF16 && d % 8 == 0 && (uintptr_t)tok_emb % 16 == 0 && (uintptr_t)pos_emb % 16 == 0 &&
                    (uintptr_t)h % 16 == 0 && (uintptr_t)hb % 16 == 0;
+  if (hbtiled && (!vec || !hb || q_len != 1 || B > 32 || d % 32 != 0))
+    return kw_set_error_msg(KW_EINVAL, "kw_embed: KW_EMBED_HB_TILED needs hb, q_len 1, B <= 32, bf16 tables, d % 32 == 0, "
+                                       "16-B aligned buffers");
   if (vec) {
     const int64_t pieces = d / 8;
     const unsigned threads = (unsigned)std::min<int64_t>(256, (pieces + 63) / 64 * 64);
     hipLaunchKernelGGL(embed_bf16x8_kernel, grid, dim3(threads), 0, s, ids, ids_stride, (int)q_len, cur_len,
-                       (const bf16_t*)tok_emb, (const bf16_t*)pos_emb, (int)d, h, (bf16_t*)hb);
+                       (const bf16_t*)tok_emb, (const bf16_t*)pos_emb, (int)d, h, (bf16_t*)hb,
+                       hbtiled ? (int)((B + 15) / 16) : 0);
   } else if (dtype == KW_DT_F32)
     hipLaunchKernelGGL(embed_kernel<float>, grid, dim3(256), 0, s, ids, ids_stride, (int)q_len, cur_len,
                        (const float*)tok_emb, (const float*)pos_emb, (int)d, h, (bf16_t*)hb);

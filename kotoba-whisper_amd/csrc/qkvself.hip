@@ -50,6 +50,7 @@ struct QSP {
   unsigned long long* gran;  // [M][3d/2]
   int* err;
   bf16_t* out;
+  int out_t;  // out fragment-major over out_t row tiles (a KW_LD_TILED call: x and out); 0: [M][d]
 };
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void qkv_self_kernel(QSP p) {
@@ -180,7 +181,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void q
     const float f0 = __builtin_amdgcn_exp2f(st[0] - m), f1 = __builtin_amdgcn_exp2f(st[1] - m);  // -inf wave -> 0
     const float l = fmaf(st[2], f0, st[3] * f1);
     const float o = fmaf(ared[ps][0][ptid], f0, ared[ps][1][ptid] * f1);
-    p.out[(int64_t)b * d + h * HD + ptid] = f2bf(o / l);
+    p.out[p.out_t ? kw_tiled_off(b, h * HD + ptid, p.out_t) : (int64_t)b * d + h * HD + ptid] = f2bf(o / l);
   }
   KW_QS_STAMP(7);
 }
@@ -208,7 +209,7 @@ extern "C" int kw_dec_qkv_self_supported(int64_t M, int64_t d, int64_t H) {
 extern "C" int kw_dec_qkv_self(const kw_dec_qkv_self_args* a, kw_stream_t stream) {
   if (!a || !a->x || !a->W || !a->ln_colsum || !a->k_cache || !a->v_cache || !a->cur_len || !a->out || !a->workspace)
     return kw_set_error_msg(KW_EINVAL, "kw_dec_qkv_self: null pointer");
-  if (!qs_shape_ok(a->M, a->d, a->H) || a->ldx < a->d || a->ldx % 8 || (uintptr_t)a->x % 16 || a->t_max < 1 ||
+  if (!qs_shape_ok(a->M, a->d, a->H) || (a->ldx != KW_LD_TILED && (a->ldx < a->d || a->ldx % 8)) || (uintptr_t)a->x % 16 || a->t_max < 1 ||
       a->t_max > 4096)
     return kw_set_error_msg(KW_EINVAL, "kw_dec_qkv_self: M <= 32 rows, d = 64 H <= 1280, ldx % 8 == 0, 16-B aligned x");
   if (a->ws_bytes < kw_dec_qkv_self_workspace(a->M, a->d))
@@ -232,6 +233,7 @@ extern "C" int kw_dec_qkv_self(const kw_dec_qkv_self_args* a, kw_stream_t stream
   p.gran = reinterpret_cast<unsigned long long*>(a->workspace);
   p.err = reinterpret_cast<int*>(reinterpret_cast<char*>(a->workspace) + qs_gran_bytes(a->M, a->d));
   p.out = reinterpret_cast<bf16_t*>(a->out);
+  p.out_t = a->ldx == KW_LD_TILED ? (int)((a->M + 15) / 16) : 0;
   const int grid = p.n_lin + (int)((a->M * a->H + QS_PAIRS - 1) / QS_PAIRS);
   hipLaunchKernelGGL(qkv_self_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
   KW_CHECK_LAUNCH();

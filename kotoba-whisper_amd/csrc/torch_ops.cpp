@@ -115,13 +115,13 @@ void gemm(const Tensor& A, const Tensor& W, const optional<Tensor>& bias, Tensor
 }
 
 // ---- decode-step linear over packed weights -----------------------------------------------------------
-// geo = [x_offset, ldx, ln, c_offset, ldc, gelu, scale_cols, resid_row0, ldh, M, N, K]
+// geo = [x_offset, ldx, ln, c_offset, ldc, gelu, scale_cols, resid_row0, ldh, M, N, K (, epilogue flags: KW_EPI_HB_TILED)]
 void dec_linear(const Tensor& x, const Tensor& W, const optional<Tensor>& bias, const optional<Tensor>& ln_colsum,
                 optional<Tensor> C, optional<Tensor> h, optional<Tensor> hb, Tensor& workspace,
                 std::vector<int64_t> geo, double ln_eps, double scale) {
   const char* w = "kw_dec_linear";
   dev(x, w), dev(W, w), dev(bias, w), dev(ln_colsum, w), dev(C, w), dev(h, w), dev(hb, w), dev(workspace, w);
-  TORCH_CHECK_VALUE(geo.size() == 12, "kw_dec_linear: geo must hold 12 integers");
+  TORCH_CHECK_VALUE(geo.size() == 12 || geo.size() == 13, "kw_dec_linear: geo must hold 12 or 13 integers");
   TORCH_CHECK_VALUE(x.scalar_type() == at::kBFloat16 && W.scalar_type() == at::kBFloat16,
                     "kw_dec_linear takes bf16 activations and packed bf16 weights");
   kw_dec_linear_args a{};
@@ -135,7 +135,7 @@ void dec_linear(const Tensor& x, const Tensor& W, const optional<Tensor>& bias, 
   if (h.has_value()) {
     TORCH_CHECK_VALUE(hb.has_value() && h->scalar_type() == at::kFloat && hb->scalar_type() == at::kBFloat16,
                       "RESID needs an f32 residual and a bf16 mirror");
-    a.epilogue = KW_EPI_RESID;
+    a.epilogue = KW_EPI_RESID | (geo.size() > 12 ? (int)geo[12] : 0);
     a.h = ptr<float>(*h, geo[7] * geo[8]);
     a.hb = ptr(*hb, geo[7] * geo[8]);
     a.ldh = geo[8];
@@ -194,11 +194,11 @@ void attention(const Tensor& qkv, int64_t B, int64_t H, int64_t T, int64_t hd, T
 }
 
 void embed(const Tensor& ids, int64_t B, int64_t q_len, const Tensor& cur_len, const Tensor& tok_emb,
-           const Tensor& pos_emb, Tensor& h, optional<Tensor> hb) {
+           const Tensor& pos_emb, Tensor& h, optional<Tensor> hb, int64_t flags) {
   const char* w = "kw_embed";
   dev(ids, w), dev(cur_len, w), dev(tok_emb, w), dev(pos_emb, w), dev(h, w), dev(hb, w);
   c10::DeviceGuard g(ids.device());
-  check(kw_embed(dt_of(tok_emb), ptr<const int64_t>(ids), ids.stride(0), B, q_len, ptr<const int32_t>(cur_len),
+  check(kw_embed(dt_of(tok_emb) | (int)flags, ptr<const int64_t>(ids), ids.stride(0), B, q_len, ptr<const int32_t>(cur_len),
                  ptr(tok_emb), ptr(pos_emb), tok_emb.size(1), ptr<float>(h), optr<void>(hb), stream_of(ids)),
         w);
 }
@@ -470,7 +470,7 @@ TORCH_LIBRARY(kw, m) {
   m.def("layernorm(Tensor(a!) x, Tensor gamma, Tensor beta, float eps, Tensor(b!) y, Tensor? delta) -> ()");
   m.def("attention(Tensor qkv, int B, int H, int T, int hd, Tensor(a!) out, int flags=0) -> ()");
   m.def("embed(Tensor ids, int B, int q_len, Tensor cur_len, Tensor tok_emb, Tensor pos_emb, Tensor(a!) h, "
-        "Tensor(b!)? hb) -> ()");
+        "Tensor(b!)? hb, int flags=0) -> ()");
   m.def("self_attn_step(Tensor qkv, int B, int q_len, int H, int hd, Tensor(a!) k_cache, Tensor(b!) v_cache, "
         "int t_max, Tensor cur_len, Tensor(c!) out, Tensor(d!)? workspace, Tensor? bp) -> ()");
   m.def("dec_qkv_self(Tensor x, Tensor W, Tensor? bias, Tensor ln_colsum, Tensor(a!) k_cache, Tensor(b!) v_cache, "

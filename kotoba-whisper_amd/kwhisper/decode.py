@@ -95,6 +95,13 @@ class DecodeSession:
                       and ops.xq_cross_supported(R, d, H, self.T))
         self.xc_ws = torch.zeros(((ops.xq_cross_workspace_bytes(R, d, H, self.T) + 3) // 4,), device=dev,
                                  dtype=torch.float32) if self.xc_ok else None
+        # fragment-major bf16 residual mirror (KW_LD_TILED) for the q = 1 step: the kernels that read hb there (the
+        # self / cross blocks or their LayerNorm-fused projections, fc1, the LM head or kw_dec_lm_greedy) take each
+        # fragment as one contiguous 1-KB piece, its producers (embed, o, xo, fc2) write that order -- bitwise the
+        # row-major plan.  The fused blocks then write attn in that order too, for o / xo.  Greedy rows of the bf16
+        # engine, <= 32 per session, a persistent-LM-head shape.
+        self.tiled_ok = bool(eng.packed and beams == 1 and eng.tiled_act and R <= 32 and d % 32 == 0
+                             and ops.lm_greedy_supported(R, s.vocab_size, d))
         self._graph = None
         self._graph_key = None
         self._cross_key = None
@@ -130,7 +137,7 @@ class DecodeSession:
         v._bufs, v._plans = {}, {}
         v.lin_ws = torch.zeros_like(self.lin_ws) if self.lin_ws is not None else None
         v.self_ws = torch.zeros_like(self.self_ws)
-        v.qs_ok = v.xc_ok = False
+        v.qs_ok = v.xc_ok = v.tiled_ok = False
         v.qs_ws = v.xc_ws = None
         return v
 
@@ -175,7 +182,9 @@ class DecodeSession:
                 h=torch.empty((rows, d), device=dev, dtype=torch.float32),
                 x=torch.empty((rows, d), device=dev, dtype=dt),
                 qkv=torch.empty((rows, 3 * d), device=dev, dtype=dt),
-                attn=torch.empty((rows, d), device=dev, dtype=dt),
+                # (q = 1: whole 16-row tiles, zeroed -- the tiled step plan's fused blocks write it fragment-major)
+                attn=torch.zeros((16 * ((rows + 15) // 16), d), device=dev, dtype=dt) if q == 1 else
+                torch.empty((rows, d), device=dev, dtype=dt),
                 qx=torch.empty((rows, d), device=dev, dtype=dt),
                 ffn=torch.empty((rows, s.decoder_ffn_dim), device=dev, dtype=dt),
                 # cross-attention partials + arrival counters (must start zeroed; kernels leave them zeroed)
@@ -183,7 +192,10 @@ class DecodeSession:
                                device=dev, dtype=torch.float32),
             )
             if self.eng.packed:  # bf16 mirror of the residual stream (the LayerNorm-fused linears' operand)
-                self._bufs[q]["hb"] = torch.empty((rows, d), device=dev, dtype=torch.bfloat16)
+                if q == 1 and self.tiled_ok:  # fragment-major: whole 16-row tiles, rows >= R zero and never written
+                    self._bufs[q]["hb"] = torch.zeros((16 * ((rows + 15) // 16), d), device=dev, dtype=torch.bfloat16)
+                else:
+                    self._bufs[q]["hb"] = torch.empty((rows, d), device=dev, dtype=torch.bfloat16)
         return self._bufs[q]
 
     def _gemm(self, A, W, C, M, N, K, **kw):
@@ -211,34 +223,36 @@ class DecodeSession:
             hb, h = b["hb"], b["h"]
             ws = self.lin_ws
             lin = ops.DecLinearPlan
-            seq = [("embed", q, h, hb)]
+            tiled = q == 1 and self.tiled_ok  # hb fragment-major (its readers' ldx, its writers' hb_tiled)
+            xld = ops.KW_LD_TILED if tiled else None
+            seq = [("embed", q, h, hb, tiled)]
             for li, lay in enumerate(eng.dec_layers):
                 if fused:
                     seq.append(ops.QkvSelfPlan(hb, lay["qkv_w"], rows, d, H, ln=(eps, lay["qkv_cs"]), bias=lay["qkv_b"],
                                                scale=scale, k_cache=self.kc[li], v_cache=self.vc[li], t_max=T_MAX,
-                                               cur_len=self.cur_len, out=b["attn"], workspace=self.qs_ws))
+                                               cur_len=self.cur_len, out=b["attn"], workspace=self.qs_ws, ldx=xld))
                 else:
                     seq.append(lin(hb, lay["qkv_w"], rows, 3 * d, d, ln=(eps, lay["qkv_cs"]), bias=lay["qkv_b"],
-                                   C=b["qkv"], scale=scale, scale_cols=d, workspace=ws, tag="qkv"))
+                                   C=b["qkv"], scale=scale, scale_cols=d, workspace=ws, tag="qkv", ldx=xld))
                     seq.append(("self", q, b["qkv"], li, b["attn"]))
                 seq.append(lin(b["attn"], lay["o_w"], rows, d, d, bias=lay["o_b"], resid=(h, hb, d, 0), workspace=ws,
-                               tag="o"))
+                               tag="o", hb_tiled=tiled, ldx=xld if fused else None))  # (the fused block's attn)
                 if q == 1 and self.xc_ok:
                     seq.append(ops.XqCrossPlan(hb, lay["xq_w"], rows, d, H, ln=(eps, lay["xq_cs"]), bias=lay["xq_b"],
                                                scale=scale, k=self.cross[2 * li], v=self.cross[2 * li + 1], S=self.T,
-                                               out=b["attn"], workspace=self.xc_ws))
+                                               out=b["attn"], workspace=self.xc_ws, ldx=xld))
                 else:
                     seq.append(lin(hb, lay["xq_w"], rows, d, d, ln=(eps, lay["xq_cs"]), bias=lay["xq_b"],
-                                   C=b["qx"], scale=scale, scale_cols=d, workspace=ws, tag="xq"))
+                                   C=b["qx"], scale=scale, scale_cols=d, workspace=ws, tag="xq", ldx=xld))
                     seq.append(("cross", q, b["qx"], li, b["attn"], b["ws"]))
                 seq.append(lin(b["attn"], lay["xo_w"], rows, d, d, bias=lay["xo_b"], resid=(h, hb, d, 0),
-                               workspace=ws, tag="xo"))
+                               workspace=ws, tag="xo", hb_tiled=tiled, ldx=xld if q == 1 and self.xc_ok else None))
                 seq.append(lin(hb, lay["fc1_w"], rows, s.decoder_ffn_dim, d, ln=(eps, lay["fc1_cs"]),
-                               bias=lay["fc1_b"], C=b["ffn"], gelu=True, workspace=ws, tag="fc1"))
+                               bias=lay["fc1_b"], C=b["ffn"], gelu=True, workspace=ws, tag="fc1", ldx=xld))
                 seq.append(lin(b["ffn"], lay["fc2_w"], rows, d, s.decoder_ffn_dim, bias=lay["fc2_b"],
-                               resid=(h, hb, d, 0), workspace=ws, tag="fc2"))
+                               resid=(h, hb, d, 0), workspace=ws, tag="fc2", hb_tiled=tiled))
             # final LayerNorm (folded into the packed LM head) + proj_out on the last position of every row
-            seq.append(lin(hb, eng.lm_w, B, s.vocab_size, d, ldx=q * d, x_offset=(q - 1) * d,
+            seq.append(lin(hb, eng.lm_w, B, s.vocab_size, d, ldx=xld or q * d, x_offset=(q - 1) * d,
                            ln=(eps, eng.lm_cs), bias=eng.lm_b, C=self.logits, workspace=ws, tag="lm_head"))
             self._plans[key] = seq
             return seq
@@ -275,7 +289,8 @@ class DecodeSession:
             if k == "ln":
                 ops.layernorm(p[1], p[2], p[3], s.layer_norm_eps, p[4])
             elif k == "embed":
-                ops.embed(self.ids, B, p[1], self.cur_len, eng.tok_emb, eng.dec_pos, p[2], p[3] if len(p) > 3 else None)
+                ops.embed(self.ids, B, p[1], self.cur_len, eng.tok_emb, eng.dec_pos, p[2], p[3] if len(p) > 3 else None,
+                          hb_tiled=len(p) > 4 and p[4])
             elif k == "self":
                 _, q, qkv, li, out = p
                 ops.self_attn_step(qkv, B, q, H, _HD, self.kc[li], self.vc[li], T_MAX, self.cur_len, out, self.self_ws,
@@ -447,7 +462,8 @@ class DecodeSession:
                     self._buffers(1)["hb"], self.eng.lm_w, B, s.vocab_size, s.d_model, ln=(s.layer_norm_eps, self.eng.lm_cs),
                     bias=self.eng.lm_b, suppress_mask=sampler._keep[1], begin_suppress=sampler._keep[2], ids=self.ids,
                     cur_len=self.cur_len, unfinished=self.unfinished, n_unfinished=self.n_unfinished, eos_id=sa.eos_id,
-                    pad_id=sa.pad_id, max_length=sa.max_length, begin_index=sa.begin_index, workspace=self._lmg_ws)
+                    pad_id=sa.pad_id, max_length=sa.max_length, begin_index=sa.begin_index, workspace=self._lmg_ws,
+                    ldx=ops.KW_LD_TILED if self.tiled_ok else None)
             assert getattr(step_seq[-1], "tag", None) == "lm_head"
             step_seq = step_seq[:-1]
         self.lm_greedy_last = tail is not sampler

@@ -184,6 +184,32 @@ class GemmPlan:
             L.check(_lib().kw_gemm(self._ref, _s()), "kw_gemm")
 
 
+KW_LD_TILED = -1  # a leading dimension that says: this bf16 activation operand is fragment-major (include/kwhisper.h)
+KW_EPI_HB_TILED = 0x100  # kw_dec_linear's RESID epilogue writes hb fragment-major
+KW_EMBED_HB_TILED = 0x100  # kw_embed writes hb fragment-major
+
+
+def act_tile(x: torch.Tensor) -> torch.Tensor:
+    """[M][K] (M <= 32, K % 32 == 0) -> the fragment-major order the MFMA linears take as ``KW_LD_TILED``: element
+    (m, k) is element k % 8 of 16-B piece ((k // 32) * T + m // 16) * 64 + m % 16 + 16 * ((k % 32) // 8), with
+    T = ceil(M / 16) row tiles; rows M .. 16 T - 1 are zero.  Flat, (K // 32) * T * 512 elements.  A pure index
+    permutation (tests and tools; the engine's producers write the order themselves)."""
+    M, K = x.shape
+    if not 1 <= M <= 32 or K % 32:
+        raise ValueError("act_tile: M <= 32 rows, K % 32 == 0")
+    T = (M + 15) // 16
+    p = x.new_zeros(16 * T, K)
+    p[:M] = x
+    # [tile][row][k-tile][piece][8] -> [k-tile][tile][piece][row][8]
+    return p.view(T, 16, K // 32, 4, 8).permute(2, 0, 3, 1, 4).contiguous().view(-1)
+
+
+def act_untile(t: torch.Tensor, M: int, K: int) -> torch.Tensor:
+    """The inverse of ``act_tile``: the [M][K] rows of a fragment-major buffer."""
+    T = (M + 15) // 16
+    return t.view(K // 32, T, 4, 16, 8).permute(1, 3, 0, 2, 4).reshape(16 * T, K)[:M].contiguous()
+
+
 def dec_linear_workspace_bytes(N: int, K: int) -> int:
     return _ws_bytes("dec_linear", N, K)
 
@@ -194,10 +220,11 @@ class DecLinearPlan:
     ``x``: bf16 [M][ldx] activations (x_offset elements from the start); ``ln`` = (eps, colsum f32 [N])
     fuses the LayerNorm of x's rows (gamma/beta folded into W/bias by the caller, colsum = row sums of
     the folded bf16 weight: ``ln_colsum``); STORE writes ``C`` (f32 or bf16, ldc); RESID updates
-    ``resid`` = (h f32, hb bf16 mirror, ldh, row offset)."""
+    ``resid`` = (h f32, hb bf16 mirror, ldh, row offset).  ``ldx=KW_LD_TILED``: x is fragment-major (``act_tile``;
+    M <= 32); ``hb_tiled``: RESID writes hb fragment-major (KW_EPI_HB_TILED; M <= 32, N % 32 == 0, row offset 0)."""
 
     def __init__(self, x, W, M, N, K, *, ldx=None, x_offset=0, ln=None, bias=None, C=None, ldc=None, c_offset=0,
-                 gelu=False, scale=1.0, scale_cols=0, resid=None, workspace=None, tag=None):
+                 gelu=False, scale=1.0, scale_cols=0, resid=None, workspace=None, tag=None, hb_tiled=False):
         _cuda(x, W, bias, C, workspace)
         self.tag = tag  # a name for per-kernel timing (bench.py), no effect on the call
         if x.dtype != torch.bfloat16 or W.dtype != torch.bfloat16:
@@ -228,7 +255,9 @@ class DecLinearPlan:
             _cuda(h, hb)
             if h.dtype != torch.float32 or hb.dtype != torch.bfloat16:
                 raise ValueError("RESID needs an f32 residual and a bf16 mirror")
-            a.epilogue = L.KW_EPI_RESID
+            if hb_tiled and row0:
+                raise ValueError("a fragment-major hb takes no row offset")
+            a.epilogue = L.KW_EPI_RESID | (KW_EPI_HB_TILED if hb_tiled else 0)
             a.h = h.data_ptr() + row0 * ldh * 4
             a.hb = hb.data_ptr() + row0 * ldh * 2
             a.ldh = ldh
@@ -237,6 +266,8 @@ class DecLinearPlan:
         else:
             if C is None:
                 raise ValueError("STORE needs C")
+            if hb_tiled:
+                raise ValueError("hb_tiled needs the RESID epilogue")
             a.epilogue = L.KW_EPI_STORE
             ldc = N if ldc is None else ldc
             a.C = C.data_ptr() + c_offset * C.element_size()
@@ -256,7 +287,7 @@ class DecLinearPlan:
         a.ws_bytes = workspace.numel() * workspace.element_size()
         self._keep = tuple(keep)
         geo = [x_offset, ldx, 1 if ln is not None else 0, c_offset, 0 if C is None else (ldc or N), int(bool(gelu)),
-               scale_cols, row0, ldh, M, N, K]
+               scale_cols, row0, ldh, M, N, K] + ([KW_EPI_HB_TILED] if hb_tiled else [])
         self._targs = (x, W, bias, colsum, C, h, hb, workspace, geo, float(eps), float(scale))
         self.args = a
         self._ref = ctypes.byref(a)
@@ -304,13 +335,15 @@ def attention(qkv: torch.Tensor, B: int, H: int, T: int, hd: int, out: torch.Ten
     return out
 
 
-def embed(ids, B, q_len, cur_len, tok_emb, pos_emb, h, hb=None):
-    """Decoder embedding into the f32 residual h (and its bf16 mirror hb for the bf16 engine)."""
+def embed(ids, B, q_len, cur_len, tok_emb, pos_emb, h, hb=None, hb_tiled=False):
+    """Decoder embedding into the f32 residual h (and its bf16 mirror hb for the bf16 engine; ``hb_tiled``: written
+    fragment-major, KW_EMBED_HB_TILED -- q_len 1, B <= 32)."""
     _cuda(ids, cur_len, tok_emb, pos_emb, h, hb)
+    flags = KW_EMBED_HB_TILED if hb_tiled else 0
     if _BACKEND == "torch":
-        _kw().embed(ids, B, q_len, cur_len, tok_emb, pos_emb, h, hb)
+        _kw().embed(ids, B, q_len, cur_len, tok_emb, pos_emb, h, hb, flags)
     else:
-        L.check(_lib().kw_embed(_dt(tok_emb), _p(ids), ids.stride(0), B, q_len, _p(cur_len), _p(tok_emb), _p(pos_emb),
+        L.check(_lib().kw_embed(_dt(tok_emb) | flags, _p(ids), ids.stride(0), B, q_len, _p(cur_len), _p(tok_emb), _p(pos_emb),
                                 tok_emb.shape[1], _p(h), _p(hb), _s()), "kw_embed")
 
 
@@ -345,7 +378,7 @@ class QkvSelfPlan:
     step in one launch (kw_dec_linear(qkv) then kw_self_attn_step: caches bitwise, attention within bf16 rounding).  ``x``: hb [M][ldx] bf16;
     ``W`` packed (gamma folded), ``ln`` = (eps, colsum [3d]), ``bias`` f32 [3d]; caches one layer's
     [M][H][t_max][64]; ``cur_len`` device int32 (L <= 256); ``out`` attn [M][d] bf16; ``workspace`` zero-filled
-    (qkv_self_workspace_bytes)."""
+    (qkv_self_workspace_bytes).  ``ldx=KW_LD_TILED``: x is read and out written fragment-major (``act_tile``)."""
 
     def __init__(self, x, W, M, d, H, *, ln, bias, scale, k_cache, v_cache, t_max, cur_len, out, workspace, ldx=None,
                  tag="qkv_self"):
@@ -398,7 +431,7 @@ class XqCrossPlan:
     """A pre-built ``kw_dec_xq_cross`` call: the LayerNorm-fused cross-attention query projection and the
     cross-attention step (q_len 1) in one launch (bitwise kw_dec_linear(xq) then kw_cross_attn_step).  ``x``: hb [M][ldx] bf16; ``W`` packed (gamma folded), ``ln`` = (eps, colsum [d]), ``bias``
     f32 [d]; ``k`` / ``v`` one layer's [M][H][S][64]; ``out`` attn [M][d] bf16; ``workspace`` zero-filled
-    (xq_cross_workspace_bytes)."""
+    (xq_cross_workspace_bytes).  ``ldx=KW_LD_TILED``: x is read and out written fragment-major (``act_tile``)."""
 
     def __init__(self, x, W, M, d, H, *, ln, bias, scale, k, v, S, out, workspace, ldx=None, tag="xq_cross"):
         _cuda(x, W, bias, k, v, out, workspace)

@@ -65,6 +65,8 @@ def main():
     ap.add_argument("--self-t", default="132", help="comma list of self-attention lengths (cur_len) to time")
     ap.add_argument("--backend", default="torch", choices=("torch", "ctypes"),
                     help="ctypes: call the C ABI directly (with KWHISPER_LIB=<lab build> for geometry overrides)")
+    ap.add_argument("--tiled", action="store_true",
+                    help="feed the linears and the fused blocks a fragment-major copy of their bf16 input (KW_LD_TILED)")
     a = ap.parse_args()
     ops.set_backend(a.backend)
     global EAGER
@@ -94,6 +96,9 @@ def main():
         plans = []
         for W in Ws:
             kw = dict(bias=bias, workspace=ws, ldx=F)
+            xin = hb
+            if a.tiled and name != "lm_head":  # (the LM head reads rows)
+                xin, kw["ldx"] = ops.act_tile(hb[:, :K]), ops.KW_LD_TILED
             if lna:
                 kw["ln"] = (1e-5, cs)
             if resid:
@@ -102,7 +107,7 @@ def main():
                 kw["C"] = C
             if name.startswith("fc1"):
                 kw["gelu"] = True
-            plans.append(ops.DecLinearPlan(hb, W, B, N, K, **kw))
+            plans.append(ops.DecLinearPlan(xin, W, B, N, K, **kw))
         us = timeit(plans, a.reps)
         res[name] = {"us": round(us, 2), "GBps": round(N * K * 2 / us / 1e3, 1)}
     # attention kernels (and the fused decode blocks: kw_dec_xq_cross, kw_dec_qkv_self)
@@ -124,8 +129,11 @@ def main():
         cs, bq = torch.zeros(d, device=dev), torch.zeros(d, device=dev)
         wsx = torch.zeros(ops.xq_cross_workspace_bytes(B, d, H, S) // 4 + 1, device=dev)
         hbd = hb[:, :d].contiguous()  # the engine's q = 1 residual mirror: [B][d]
+        if a.tiled:
+            hbd = ops.act_tile(hbd)
         plans = [ops.XqCrossPlan(hbd, Wq[i], B, d, H, ln=(1e-5, cs), bias=bq, scale=0.125, k=cross[i][0], v=cross[i][1],
-                                 S=S, out=out, workspace=wsx) for i in range(nl)]
+                                 S=S, out=out, workspace=wsx, ldx=ops.KW_LD_TILED if a.tiled else None)
+                 for i in range(nl)]
         us = timeit(plans, max(1, a.reps // 4))
         res["xq_cross"] = {"us": round(us, 2), "GBps": round((2 * B * H * S * 64 * 2 + d * d * 2) / us / 1e3, 1)}
         del cross, Wq, plans
@@ -147,8 +155,11 @@ def main():
             cs3, b3 = torch.zeros(3 * d, device=dev), torch.zeros(3 * d, device=dev)
             qws = torch.zeros(ops.qkv_self_workspace_bytes(B, d) // 4 + 1, device=dev)
             hbd = hb[:, :d].contiguous()  # the engine's q = 1 residual mirror: [B][d]
+            if a.tiled:
+                hbd = ops.act_tile(hbd)
             plans = [ops.QkvSelfPlan(hbd, Wqkv[i], B, d, H, ln=(1e-5, cs3), bias=b3, scale=0.125, k_cache=kc[i],
-                                     v_cache=vc[i], t_max=448, cur_len=cur, out=out, workspace=qws)
+                                     v_cache=vc[i], t_max=448, cur_len=cur, out=out, workspace=qws,
+                                     ldx=ops.KW_LD_TILED if a.tiled else None)
                      for i in range(nl)]
             res[f"qkv_self_t{t}"] = {"us": round(timeit(plans, a.reps), 2)}
             del Wqkv, plans
