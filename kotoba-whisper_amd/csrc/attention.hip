@@ -28,17 +28,7 @@ typedef __attribute__((ext_vector_type(4))) short s16x4;
 typedef __attribute__((ext_vector_type(2))) unsigned int v2u32;
 typedef __attribute__((ext_vector_type(4))) unsigned int v4u32;
 
-__device__ __forceinline__ uint32_t lds_u32(const void* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
-}
-
 namespace {
-
-
-__device__ __forceinline__ void glds16(const void* g, char* lds_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
-}
 
 // lane ^ 32 reductions by v_permlane32_swap (a VALU half-exchange; no LDS round trip like ds_bpermute):
 // with both operands = v, one result holds the lane's own value and the other its partner's
@@ -963,37 +953,82 @@ __global__ __launch_bounds__(256) void cross_attn_kernel(const T* __restrict__ q
   publish_and_combine<T>(ws + (int64_t)row * ns * (HD + 2), cnt + row, ns, split, m, l, o, orow, &last);
 }
 
-// Cross-attention, bf16, one query row per (row, chunk) workgroup -- as cross_attn_kernel, but the chunk's K
-// rows arrive by LDS-DMA (global_load_lds_dwordx4, non-temporal) and V by register loads (r02: 44.4-44.6 us vs
-// 45.4-45.6 for register loads only, 50.3 with V by LDS-DMA too at 2 workgroups per CU).  Wave w's DMA
-// instruction j moves keys k0 + 32 j + 8 w + (0..7) (1 KB, lane = (key, 16-B piece)) to LDS piece 4 j + w and
-// each lane reads back exactly its own 16 B, so the arithmetic is wave_row_bf16's (bitwise the rows of
-// cross_attn_kernel / cross_attn_multi_kernel).  r03 (tools/lab/xa_lab.hip, large-v3 B = 32 over 32 distinct
-// layers): the same grid only STREAMING its bytes reaches 38-40 us (6.1-6.5 TB/s); the softmax work after
-// the loads land costs the rest -- log2-unit scores with per-wave references (no mid-chunk barrier) and DPP
-// sums take ~2 us of it, the granule combine (no store drain / counter round trips) another ~1 us.
+// Cross-attention, bf16, one query row per (row, chunk) workgroup: the chunk grid.  One body, cross_chunk<QG>,
+// is the (row, chunk) work of both cross_attn_dma_kernel (the query is a row in memory) and xq_cross_kernel (the
+// query is handed over in-launch by projection workgroups); the two kernels only map blockIdx to (row, chunk),
+// name the query and the output element, and xq_cross_kernel re-arms its query granules.  So the two compute the
+// same bits by construction, and a change to the chunk schedule or the hand-off is made once.
+//
+// As cross_attn_kernel, but the chunk's K rows arrive by LDS-DMA (global_load_lds_dwordx4, non-temporal) and V by
+// register loads (r02: 44.4-44.6 us vs 45.4-45.6 for register loads only, 50.3 with V by LDS-DMA too at 2
+// workgroups per CU).  Wave w's DMA instruction j moves keys k0 + 32 j + 8 w + (0..7) (1 KB, lane = (key, 16-B
+// piece)) to LDS piece 4 j + w and each lane reads back exactly its own 16 B, so the arithmetic is
+// wave_row_bf16's (bitwise the rows of cross_attn_kernel / cross_attn_multi_kernel).  r03 (tools/lab/xa_lab.hip,
+// large-v3 B = 32 over 32 distinct layers): the same grid only STREAMING its bytes reaches 38-40 us (6.1-6.5
+// TB/s); the softmax work after the loads land costs the rest -- log2-unit scores with per-wave references (no
+// mid-chunk barrier) and DPP sums take ~2 us of it, the granule combine (no store drain / counter round trips)
+// another ~1 us.
 #ifndef KW_XA_DMA
 #define KW_XA_DMA 1  // 0: register loads only (cross_attn_kernel)
 #endif
 constexpr int XA_DMA = KW_XA_DMA;
 
-// a workgroup barrier without __syncthreads()'s fence (which waits vmcnt(0), draining loads still in flight);
-// compiler barriers on both sides keep every memory access (LDS reads of DMA'd data) on its side
-__device__ __forceinline__ void raw_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ void glds16_nt(const void* g, char* lds_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_base, 16, 0, 2);
-}
 __device__ __forceinline__ u32x4 lds_rd16(const char* p) {
   u32x4 v;
   asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_u32(p)) : "memory");
   return v;
+}
+
+// Keys [k0, k1) of one (row, head) pair -- chunk `split` of its ns -- against the pair's query, then the chunk-partial
+// hand-off / combine (wave_partials_combine over the pair's granules gr; the last chunk writes out_el(), this lane's
+// output element -- a callable, so its address arithmetic stays behind the loads).  kb / vb: the pair's K / V rows;
+// kv: 32 KB of LDS for the K pieces.
+// The query is `query`: 64 bf16 (!QG), or with QG the pair's 32 {bf16 x 2, tag} granules, which the projection
+// workgroups of the same launch publish.  Its loads go out FIRST, then every K piece and V row of the chunk, and
+// it is checked once the K pieces have landed: by then the projection (a few us; the first wave of chunks needs
+// ~10 us to stream its 64 MB) has published, so the K / V stream never waits on it.
+template <bool QG, typename OutEl>
+__device__ __forceinline__ void cross_chunk(const void* query, const bf16_t* kb, const bf16_t* vb, int k0, int k1,
+                                            unsigned long long* gr, int ns, int split, char* kv, float (*red)[64],
+                                            float* stat, OutEl out_el, int* err) {
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int sub = lane & 7, slot = wave * 8 + (lane >> 3);
+  // inline asm for the query loads: hipcc would otherwise drain every LDS-DMA in flight before their use
+  unsigned long long g[4];
+  u32x4 qraw;
+  const unsigned long long* q4 = reinterpret_cast<const unsigned long long*>(query) + sub * 4;
+  if constexpr (QG) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(g[i]) : "v"(q4 + i) : "memory");
+  } else {
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qraw) : "v"(reinterpret_cast<const bf16_t*>(query) + sub * 8) : "memory");
+  }
+  // every group j is issued (clamped keys: the host guarantees k1 - k0 > 224, so group 7 has valid keys)
+#pragma unroll
+  for (int j = 0; j < 8; ++j) glds16_nt(kb + (int64_t)min(k0 + slot + 32 * j, k1 - 1) * HD + sub * 8, kv + (4 * j + wave) * 1024);
+  u32x4 vr[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) vr[j] = ld_row8<bf16_t>(vb + (int64_t)min(k0 + slot + 32 * j, k1 - 1) * HD + sub * 8).u[0];
+  // q and this wave's K pieces landed (V may fly)
+  if constexpr (QG) {
+    asm volatile("s_waitcnt vmcnt(8)" : "+v"(g[0]), "+v"(g[1]), "+v"(g[2]), "+v"(g[3]) :: "memory");
+    qraw = wait_query_granules(q4, g, err);
+  } else {
+    asm volatile("s_waitcnt vmcnt(8)" : "+v"(qraw) :: "memory");
+  }
+  float ql[8];
+  query_log2(qraw, ql);
+  // no barrier: each lane reads back only the 16 B its own DMA wrote, complete at the wave's vmcnt
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  u32x4 kr[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) kr[j] = lds_rd16(kv + (4 * j + wave) * 1024 + lane * 16);
+  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kr[0]), "+v"(kr[1]), "+v"(kr[2]), "+v"(kr[3]), "+v"(kr[4]), "+v"(kr[5]),
+               "+v"(kr[6]), "+v"(kr[7]));
+  float mw, lw, acc[8];
+  wave_row_bf16(ql, kr, vr, k0, k1, slot, 8, mw, lw, acc);
+  wave_partials_combine(gr, ns, split, mw, lw, acc, red, stat, out_el(), err);
 }
 
 __global__ __launch_bounds__(256) void cross_attn_dma_kernel(const bf16_t* __restrict__ q, int q_len, int H,
@@ -1006,146 +1041,65 @@ __global__ __launch_bounds__(256) void cross_attn_dma_kernel(const bf16_t* __res
   __shared__ float stat[8];
   const int row = blockIdx.x, split = blockIdx.y, ns = gridDim.y;
   const int h = row % H, bq = row / H, b = bq / q_len;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int sub = lane & 7, slot = wave * 8 + (lane >> 3);
   const int k0 = split * chunk, k1 = min(S, k0 + chunk);
-  const bf16_t* kb = kc + ((int64_t)b * H + h) * S * HD;
-  const bf16_t* vb = vc + ((int64_t)b * H + h) * S * HD;
-  // the query first (inline asm: hipcc would otherwise drain every LDS-DMA in flight before its use)
-  u32x4 qraw;
-  asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qraw) : "v"(q + (int64_t)bq * H * HD + h * HD + sub * 8) : "memory");
-  // every group j is issued (clamped keys: the host guarantees k1 - k0 > 224, so group 7 has valid keys)
-#pragma unroll
-  for (int j = 0; j < 8; ++j) glds16_nt(kb + (int64_t)min(k0 + slot + 32 * j, k1 - 1) * HD + sub * 8, kv + (4 * j + wave) * 1024);
-  u32x4 vr[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) vr[j] = ld_row8<bf16_t>(vb + (int64_t)min(k0 + slot + 32 * j, k1 - 1) * HD + sub * 8).u[0];
-  asm volatile("s_waitcnt vmcnt(8)" : "+v"(qraw) :: "memory");  // q and this wave's K pieces landed (V may fly)
-  float ql[8];
-  {
-    Row8<bf16_t> qr;
-    qr.u[0] = qraw;
-    unpack8<bf16_t>(qr, ql);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ql[i] *= LOG2E;
-  }
-  // no barrier: each lane reads back only the 16 B its own DMA wrote, complete at the wave's vmcnt
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  u32x4 kr[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) kr[j] = lds_rd16(kv + (4 * j + wave) * 1024 + lane * 16);
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kr[0]), "+v"(kr[1]), "+v"(kr[2]), "+v"(kr[3]), "+v"(kr[4]), "+v"(kr[5]),
-               "+v"(kr[6]), "+v"(kr[7]));
-  float mw, lw, acc[8];
-  wave_row_bf16(ql, kr, vr, k0, k1, slot, 8, mw, lw, acc);
-  wave_partials_combine(gran + (int64_t)row * ns * 4 * (HD + 2), ns, split, mw, lw, acc, red, stat,
-                        out + (int64_t)bq * H * HD + h * HD + (threadIdx.x & 63), err);
+  const int64_t pair = ((int64_t)b * H + h) * S * HD, el = (int64_t)bq * H * HD + h * HD;
+  cross_chunk<false>(q + el, kc + pair, vc + pair, k0, k1, gran + (int64_t)row * ns * 4 * (HD + 2), ns, split, kv, red,
+                     stat, [&] { return out + el + (threadIdx.x & 63); }, err);
 }
+
+// The launch descriptor of the bf16 one-row (q_len 1) cross-attention kernels that take their query either way:
+// xq_cross_kernel and cross_attn_row_kernel<QG>.
+struct CRP {
+  const bf16_t* q;           // [rows][64] (row stride d) when the query is in memory (cross_attn_row_kernel<false>)
+  unsigned long long* qg;    // [M][d/2] query granules when the projection runs in the launch
+  unsigned long long* gran;  // the chunk grid's chunk-partial granules (xq_cross_kernel)
+  const bf16_t* kc;
+  const bf16_t* vc;
+  int H, d, S, chunk, ns, n_lin;
+  int* err;
+  bf16_t* out;
+  int out_t;  // out fragment-major over out_t row tiles (kw_dec_xq_cross with KW_LD_TILED); 0: row stride d
+  ProjArgs proj;  // the query projection (rows M = proj.M), when it runs in the launch
+};
 
 // ------------------------------------------------------------------------------------------------
 // The cross-attention block's query projection and attention step in ONE launch (bf16 engine, q_len 1):
 // the LayerNorm-fused q projection (TF/models/whisper/modeling_whisper.py:483 encoder_attn_layer_norm,
-// :309 q * head_dim^-0.5) and cross_attn_dma_kernel's attention over the item's encoder K/V (:323-356) --
-// what kw_dec_linear(xq) followed by kw_cross_attn_step computes in two launches, bit for bit.
+// :309 q * head_dim^-0.5) and the chunk grid's attention over the item's encoder K/V (:323-356) --
+// what kw_dec_linear(xq) followed by kw_cross_attn_step computes in two launches, bit for bit (the attention IS
+// cross_attn_dma_kernel's code, cross_chunk).
 //
 //  * workgroups [0, n_lin): the query projection, 16 columns each -- dec_linear's arithmetic on 4 waves
 //    (decproj.h: its 8 waves as virtual waves, reduced in the same order), published as 8-byte
 //    {bf16 x 2, tag} granules [M][d/2];
-//  * workgroups [n_lin, n_lin + M H ns): cross_attn_dma_kernel's (row, chunk) work in its dispatch order
-//    (every row's chunk 0 first, the combining last chunk last).  The query's 4 granules per lane are loaded
-//    BEFORE the chunk's K / V stream is issued and checked once the K pieces land: by then the projection
-//    (a few us; the first wave of chunks needs ~10 us to stream its 64 MB) has published, so the K / V stream
-//    does not wait on it.  The row's last chunk re-arms the row's query granules after its combine (every
-//    other chunk of the row has read them: their partials, polled by the combine, depend on them).
+//  * workgroups [n_lin, n_lin + M H ns): cross_chunk<true> per (row, chunk) in cross_attn_dma_kernel's dispatch
+//    order (every row's chunk 0 first, the combining last chunk last).  The row's last chunk re-arms the row's
+//    query granules after its combine (every other chunk of the row has read them: their partials, polled by the
+//    combine, depend on them).
 // The projection workgroups wait for nothing and lead the dispatch order; a chunk waits only for them and for
-// earlier chunks of its row (cross_attn_dma_kernel's combine), so every wait is on work dispatched before it
-// -- resident or finished, whatever else shares the GPU (no co-residency assumption).
+// earlier chunks of its row (the combine), so every wait is on work dispatched before it -- resident or
+// finished, whatever else shares the GPU (no co-residency assumption).
 // Polls are bounded: a timeout raises the error word and the row's output is NaN.
-struct XQP {
-  const bf16_t* x;
-  int64_t ldx;
-  float ln_eps;
-  const float* ln_colsum;
-  const bf16x8* W;
-  const float* bias;
-  float scale;
-  int M, d, H, n_lin, S, chunk, ns;
-  const bf16_t* kc;
-  const bf16_t* vc;
-  unsigned long long* qg;    // [M][d/2] query granules
-  unsigned long long* gran;  // cross_attn_dma_kernel's chunk-partial granules
-  int* err;
-  bf16_t* out;
-  int out_t;  // out fragment-major over out_t row tiles (a KW_LD_TILED call: x and out); 0: [M][d]
-};
-
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void xq_cross_kernel(XQP p) {
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void xq_cross_kernel(CRP p) {
   __shared__ __attribute__((aligned(16))) char kv[32 * 1024];  // K pieces (chunks) / reduction scratch (projection)
   __shared__ float red[4][64];
   __shared__ float stat[8];
   if ((int)blockIdx.x < p.n_lin) {
-    proj_publish_granules<false>(ProjArgs{p.x, p.ldx, p.M, p.d, p.d, p.ln_eps, p.ln_colsum, p.W, p.bias, p.scale, p.d, p.err + 1},
-                                 blockIdx.x, kv, p.qg);
+    proj_publish_granules<false>(p.proj, blockIdx.x, kv, p.qg);
     return;
   }
-  const int rows = p.M * p.H;
+  const int rows = p.proj.M * p.H;
   const int r = blockIdx.x - p.n_lin;
   const int row = r % rows, split = r / rows, ns = p.ns;
   const int h = row % p.H, b = row / p.H;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int sub = lane & 7, slot = wave * 8 + (lane >> 3);
+  const int tid = threadIdx.x;
   const int k0 = split * p.chunk, k1 = min(p.S, k0 + p.chunk);
-  const bf16_t* kb = p.kc + ((int64_t)b * p.H + h) * p.S * HD;
-  const bf16_t* vb = p.vc + ((int64_t)b * p.H + h) * p.S * HD;
+  const int64_t pair = ((int64_t)b * p.H + h) * p.S * HD;
   unsigned long long* qg = p.qg + (int64_t)b * (p.d / 2) + h * 32;
-  // the query's granules first, then every K piece (LDS-DMA) and V row (inline asm for the query loads: hipcc
-  // would otherwise drain the LDS-DMA in flight before their use)
-  unsigned long long g[4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-    asm volatile("global_load_dwordx2 %0, %1, off sc1" : "=v"(g[i]) : "v"(qg + sub * 4 + i) : "memory");
-#pragma unroll
-  for (int j = 0; j < 8; ++j) glds16_nt(kb + (int64_t)min(k0 + slot + 32 * j, k1 - 1) * HD + sub * 8, kv + (4 * j + wave) * 1024);
-  u32x4 vr[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) vr[j] = ld_row8<bf16_t>(vb + (int64_t)min(k0 + slot + 32 * j, k1 - 1) * HD + sub * 8).u[0];
-  asm volatile("s_waitcnt vmcnt(8)" : "+v"(g[0]), "+v"(g[1]), "+v"(g[2]), "+v"(g[3]) :: "memory");  // q + K landed
-  bool ok = ((g[0] & g[1] & g[2] & g[3]) >> 32) == 1ull;
-  for (int it = 0; __builtin_amdgcn_ballot_w64(!ok) != 0; ++it) {  // the projection not yet published: poll
-    if (it >= XG_SPIN_LIMIT) {
-      if (!ok) {
-        __hip_atomic_store(p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-        for (int i = 0; i < 4; ++i) g[i] = 0x7fc07fc0ull | (1ull << 32);  // bf16 NaN pairs: the row fails loudly
-        ok = true;
-      }
-      continue;
-    }
-    __builtin_amdgcn_s_sleep(KW_POLL_SLEEP);
-#pragma unroll
-    for (int i = 0; i < 4; ++i) g[i] = peek_granule(qg + sub * 4 + i);
-    ok = ((g[0] & g[1] & g[2] & g[3]) >> 32) == 1ull;
-  }
-  float ql[8];
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const uint32_t wq = (uint32_t)g[i];
-    ql[2 * i] = __uint_as_float(wq << 16) * LOG2E;
-    ql[2 * i + 1] = __uint_as_float(wq & 0xffff0000u) * LOG2E;
-  }
-  // no barrier: each lane reads back only the 16 B its own DMA wrote, complete at the wave's vmcnt
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  u32x4 kr[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) kr[j] = lds_rd16(kv + (4 * j + wave) * 1024 + lane * 16);
-  asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(kr[0]), "+v"(kr[1]), "+v"(kr[2]), "+v"(kr[3]), "+v"(kr[4]), "+v"(kr[5]),
-               "+v"(kr[6]), "+v"(kr[7]));
-  float mw, lw, acc[8];
-  wave_row_bf16(ql, kr, vr, k0, k1, slot, 8, mw, lw, acc);
-  wave_partials_combine(p.gran + (int64_t)row * ns * 4 * (HD + 2), ns, split, mw, lw, acc, red, stat,
-                        p.out + (p.out_t ? kw_tiled_off(b, h * HD + (tid & 63), p.out_t) : (int64_t)b * p.d + h * HD + (tid & 63)), p.err);
+  cross_chunk<true>(
+      qg, p.kc + pair, p.vc + pair, k0, k1, p.gran + (int64_t)row * ns * 4 * (HD + 2), ns, split, kv, red, stat,
+      [&] { return p.out + (p.out_t ? kw_tiled_off(b, h * HD + (tid & 63), p.out_t) : (int64_t)b * p.d + h * HD + (tid & 63)); },
+      p.err);
   if (split == ns - 1 && tid < 32)  // re-arm the row's query for the next launch (every chunk has read it)
     __hip_atomic_store(qg + tid, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -1153,24 +1107,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void x
 // ------------------------------------------------------------------------------------------------
 // Cross-attention, bf16, q_len 1, ONE workgroup per (row, head) pair looping over the pair's chunks with the
 // next chunk's K / V in flight while the current one is computed -- used when every pair fits on the device
-// at once (large-v3 B = 32: 640 workgroups, 3 per CU).  The chunk-per-workgroup grid (cross_attn_dma_kernel)
-// streams in rounds: every workgroup of a round lands its last byte at about the same time, then computes
-// while the memory system idles (tools/lab/xa_lab.hip: the same grid only streaming is 38-40 us, with the
-// softmax 44-46).  Here each wave keeps its own running softmax over the pair's chunks (log2-unit scores,
-// wave_row_bf16, merged online with exp2 rescales); the four waves merge once at the end -- no chunk
-// partials, no combine, no workspace.  With QG the query comes from xq_cross's granules (projection
-// workgroups [0, n_lin) first, as xq_cross_kernel) and the pair re-arms them after use.
-struct CRP {
-  const bf16_t* q;           // [rows][64] (row stride d) when !QG
-  unsigned long long* qg;    // [M][d/2] query granules when QG
-  const bf16_t* kc;
-  const bf16_t* vc;
-  int H, d, S, chunk, ns, n_lin;
-  int* err;
-  bf16_t* out;
-  int out_t;  // out fragment-major over out_t row tiles (kw_dec_xq_cross with KW_LD_TILED); 0: row stride d
-  ProjArgs proj;  // QG: the query projection
-};
+// at once (large-v3 B = 32: 640 workgroups, 3 per CU).  The chunk grid (cross_chunk) streams in rounds: every
+// workgroup of a round lands its last byte at about the same time, then computes while the memory system idles
+// (tools/lab/xa_lab.hip: the same grid only streaming is 38-40 us, with the softmax 44-46).  Here each wave
+// keeps its own running softmax over the pair's chunks (log2-unit scores, wave_row_bf16, merged online with exp2
+// rescales); the four waves merge once at the end -- no chunk partials, no combine, no workspace.  With QG the
+// query comes from the projection workgroups [0, n_lin) of the launch through the same hand-off as
+// xq_cross_kernel's (wait_query_granules) and the pair re-arms the granules after use.
 
 // a chunk's 16-B pieces of the pair's K or V rows (lane: row k0 + slot + 32 j, bytes voff = (slot * 64 + sub * 8) * 2
 // of it) through a buffer resource over the pair's S rows: rows past S read as 0 (masked like every row past the
@@ -1240,33 +1183,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
   row_issue(rsk, 0, voff, r0);
   row_issue(rsv, 0, voff, r1);
   if (ns > 1) row_issue(rsk, chunk, voff, r2);
-  if constexpr (QG) {
-    bool ok = ((g[0] & g[1] & g[2] & g[3]) >> 32) == 1ull;
-    for (int it = 0; __builtin_amdgcn_ballot_w64(!ok) != 0; ++it) {  // the projection not yet published: poll
-      if (it >= XG_SPIN_LIMIT) {
-        if (!ok) {
-          __hip_atomic_store(p.err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-          for (int i = 0; i < 4; ++i) g[i] = 0x7fc07fc0ull | (1ull << 32);  // bf16 NaN pairs: the row fails loudly
-          ok = true;
-        }
-        continue;
-      }
-      __builtin_amdgcn_s_sleep(KW_POLL_SLEEP);
-#pragma unroll
-      for (int i = 0; i < 4; ++i) g[i] = peek_granule(qg + sub * 4 + i);
-      ok = ((g[0] & g[1] & g[2] & g[3]) >> 32) == 1ull;
-    }
-    qraw = u32x4{(uint32_t)g[0], (uint32_t)g[1], (uint32_t)g[2], (uint32_t)g[3]};
-  }
+  if constexpr (QG) qraw = wait_query_granules(qg + sub * 4, g, p.err);
   float ql[8];
-  {
-    Row8<bf16_t> qr;
-    qr.u[0] = qraw;
-    unpack8<bf16_t>(qr, ql);
-#pragma unroll
-    for (int i = 0; i < 8; ++i) ql[i] *= LOG2E;
-  }
+  query_log2(qraw, ql);
   float M = -INFINITY, Lr = 0.f, A[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) A[i] = 0.f;
@@ -1721,11 +1640,23 @@ __global__ __launch_bounds__(256) void self_attn_step1(const T* __restrict__ qkv
   publish_and_combine<T>(ws + (int64_t)bh * 2 * (HD + 2), cnt + bh, ns, split, m, l, o, orow, &last);
 }
 
-int cross_splits(int64_t S) {
-  int ns = (int)((S + 255) / 256);  // <= 256 keys per chunk (attend_chunk); <= 8 chunks (combine)
-  if (ns < 1) ns = 1;
-  return ns;
-}
+// The chunk schedule of the cross-attention over S keys for `rows` (row, head) pairs: ns = ceil(S / 256) chunks of
+// chunk = ceil(S / ns) keys (<= 256: attend_chunk; S <= 2048 gives <= 8 chunks: the combines), the last one of `last`.
+struct CrossGeo {
+  int64_t rows, S;
+  int ns, chunk, last;
+  CrossGeo(int64_t rows_, int64_t S_) : rows(rows_), S(S_) {
+    ns = (int)((S + 255) / 256);
+    if (ns < 1) ns = 1;
+    chunk = (int)((S + ns - 1) / ns);
+    last = (int)(S - (int64_t)(ns - 1) * chunk);
+  }
+  // the chunk grid (cross_chunk: cross_attn_dma_kernel, xq_cross_kernel) issues all 8 key groups of a chunk: the
+  // last group of every chunk must hold a valid key
+  bool dma_ok() const { return chunk > 224 && chunk <= 256 && last > 224; }
+  // the pair kernel (cross_attn_row_kernel) checks only key group ROW_JV against the chunk end
+  bool row_groups_ok() const { return chunk > 32 * ROW_JV && last > 32 * ROW_JV; }
+};
 
 }  // namespace
 
@@ -1796,27 +1727,39 @@ extern "C" int kw_self_attn_step(int dtype, const void* qkv, int64_t B, int64_t 
   return KW_OK;
 }
 
-static size_t cross_partials_bytes(int64_t B, int64_t q_len, int64_t H, int64_t S) {
-  return (size_t)(B * q_len * H) * cross_splits(S) * (HD + 2) * sizeof(float);
-}
+static size_t align64(size_t n) { return (n + 63) & ~(size_t)63; }
 
-// workspace: f32 partials [rows][ns][HD+2] | arrival counters [rows] (publish_and_combine kernels) | status word,
-// fault-injection word (kw_dec_xq_cross's projection),
-// padded to 64 B | 8-byte granules [rows][ns][4 waves][HD+2] (cross_attn_dma_kernel, xq_cross_kernel); every region
-// zero before first use
-static size_t cross_granule_offset(int64_t B, int64_t q_len, int64_t H, int64_t S) {
-  const size_t head = cross_partials_bytes(B, q_len, H, S) + (size_t)(B * q_len * H) * sizeof(int) + 2 * sizeof(int);
-  return (head + 63) & ~(size_t)63;
-}
+// The cross-attention workspace of `rows` (row, head) pairs, byte offsets: f32 partials [rows][ns][HD+2] | arrival
+// counters [rows] (publish_and_combine kernels) | status word | fault-injection word (kw_dec_xq_cross's projection) |
+// pad to 64 B | 8-byte wave granules [rows][ns][4 waves][HD+2] (the chunk grid: cross_chunk) -- kw_cross_attn_step's
+// workspace ends here -- | pad to 64 B | query granules [M][d/2] (n_qg of them: kw_dec_xq_cross).  Every region is
+// zero before first use.
+struct CrossLayout {
+  size_t partials = 0, counters, status, fault, wave_gran, step_end, query_gran, fused_end;
+  explicit CrossLayout(const CrossGeo& g, int64_t n_qg = 0) {
+    const size_t part_bytes = (size_t)g.rows * g.ns * (HD + 2) * sizeof(float);
+    counters = part_bytes;
+    status = counters + (size_t)g.rows * sizeof(int);
+    fault = status + sizeof(int);
+    wave_gran = align64(fault + sizeof(int));
+    step_end = wave_gran + 8 * part_bytes;  // an 8-byte granule per f32 of a partial, per wave: 2 x 4
+    query_gran = align64(step_end);
+    fused_end = query_gran + (size_t)n_qg * sizeof(unsigned long long);
+  }
+  template <typename T>
+  T* at(void* ws, size_t off) const {
+    return reinterpret_cast<T*>(reinterpret_cast<char*>(ws) + off);
+  }
+};
 
 extern "C" size_t kw_cross_attn_workspace(int64_t B, int64_t q_len, int64_t H, int64_t hd, int64_t S) {
   (void)hd;
-  return cross_granule_offset(B, q_len, H, S) + 8 * cross_partials_bytes(B, q_len, H, S);  // granules per wave
+  return CrossLayout(CrossGeo(B * q_len * H, S)).step_end;
 }
 
 extern "C" size_t kw_cross_attn_status_offset(int64_t B, int64_t q_len, int64_t H, int64_t hd, int64_t S) {
   (void)hd;
-  return cross_partials_bytes(B, q_len, H, S) + (size_t)(B * q_len * H) * sizeof(int);
+  return CrossLayout(CrossGeo(B * q_len * H, S)).status;
 }
 
 // cross_attn_row_kernel when one round of pair workgroups covers the device -- at least one per CU, all resident
@@ -1824,25 +1767,36 @@ extern "C" size_t kw_cross_attn_status_offset(int64_t B, int64_t q_len, int64_t 
 constexpr int ROW_NS = 6;  // cross_attn_row_kernel's chunk count (S = 1500)
 
 template <bool QG>
-static bool row_kernel_fits(int64_t rows, int64_t S) {
-  const int ns = cross_splits(S);
-  const int64_t chunk = (S + ns - 1) / ns;
-  if (chunk <= 32 * ROW_JV || S - (int64_t)(ns - 1) * chunk <= 32 * ROW_JV) return false;  // row_fold's key groups
-  static int ncu = 0, per_cu = 0, off = -1;
+static bool row_kernel_fits(const CrossGeo& g) {
+  if (!g.row_groups_ok()) return false;
+  static int per_cu = 0, off = -1;
   if (off < 0) {
     const char* e = getenv("KW_CROSS_ROW");
     off = (e && e[0] == '0') ? 1 : 0;
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&cross_attn_row_kernel<QG, ROW_NS>), 256,
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, reinterpret_cast<const void*>(&cross_attn_row_kernel<QG, ROW_NS>), 256,
                                                      0) != hipSuccess)
-      ncu = per_cu = 0;
+      per_cu = 0;
   }
-  return !off && ns == ROW_NS && ncu > 0 && rows >= ncu && rows <= (int64_t)ncu * per_cu;
+  const int ncu = kw_device_cus();  // 0 (unknown): the pair kernel is off
+  return !off && g.ns == ROW_NS && ncu > 0 && g.rows >= ncu && g.rows <= (int64_t)ncu * per_cu;
+}
+
+// the launch descriptor's fields that kw_cross_attn_step and kw_dec_xq_cross fill alike (the query -- a row pointer, or
+// the granules and the projection that publishes them -- is the caller's)
+static CRP cross_crp(const CrossGeo& g, const CrossLayout& L, void* ws, int64_t H, const void* k, const void* v, void* out) {
+  CRP p{};
+  p.gran = L.at<unsigned long long>(ws, L.wave_gran);
+  p.kc = (const bf16_t*)k;
+  p.vc = (const bf16_t*)v;
+  p.H = (int)H, p.d = (int)(H * HD), p.S = (int)g.S, p.chunk = g.chunk, p.ns = g.ns;
+  p.err = L.at<int>(ws, L.status);
+  p.out = (bf16_t*)out;
+  return p;
 }
 
 extern "C" int kw_cross_attn_pair_kernel(int64_t rows, int64_t S, int fused) {
-  return (fused ? row_kernel_fits<true>(rows, S) : row_kernel_fits<false>(rows, S)) ? 1 : 0;
+  const CrossGeo g(rows, S);
+  return (fused ? row_kernel_fits<true>(g) : row_kernel_fits<false>(g)) ? 1 : 0;
 }
 
 extern "C" int kw_cross_attn_step(int dtype, const void* q, int64_t B, int64_t q_len, int64_t H, int64_t hd,
@@ -1851,15 +1805,15 @@ extern "C" int kw_cross_attn_step(int dtype, const void* q, int64_t B, int64_t q
   if (!q || !k || !v || !out || !workspace || B <= 0 || q_len <= 0 || H <= 0 || S <= 0)
     return kw_set_error_msg(KW_EINVAL, "kw_cross_attn_step: invalid arguments");
   if (hd != HD) return kw_set_error_msg(KW_EUNSUPPORTED, "kw_cross_attn_step: head_dim must be 64");
-  if (ws_bytes < kw_cross_attn_workspace(B, q_len, H, hd, S))
-    return kw_set_error_msg(KW_EINVAL, "kw_cross_attn_step: workspace too small");
+  const CrossGeo g(B * q_len * H, S);
+  const CrossLayout L(g);
+  if (ws_bytes < L.step_end) return kw_set_error_msg(KW_EINVAL, "kw_cross_attn_step: workspace too small");
   if (S > 2048) return kw_set_error_msg(KW_EUNSUPPORTED, "kw_cross_attn_step: S <= 2048 (8 chunks of 256)");
-  const int ns = cross_splits(S);
-  const int chunk = (int)((S + ns - 1) / ns);
+  const int ns = g.ns, chunk = g.chunk;
   hipStream_t s = (hipStream_t)stream;
-  dim3 grid((unsigned)(B * q_len * H), (unsigned)ns);
-  float* part = (float*)workspace;
-  int* cnt = (int*)((char*)workspace + cross_partials_bytes(B, q_len, H, S));
+  dim3 grid((unsigned)g.rows, (unsigned)ns);
+  float* part = L.at<float>(workspace, L.partials);
+  int* cnt = L.at<int>(workspace, L.counters);
   if (dtype == KW_DT_BF16 && q_len > 1 && q_len <= 4) {  // several rows per item (prefill, beams): one K/V pass
     const dim3 gm((unsigned)(B * H), (unsigned)ns);
     hipLaunchKernelGGL((cross_attn_multi_kernel<bf16_t, 4>), gm, dim3(256), 0, s, (const bf16_t*)q, (int)q_len, (int)H,
@@ -1879,20 +1833,14 @@ extern "C" int kw_cross_attn_step(int dtype, const void* q, int64_t B, int64_t q
     const dim3 gm((unsigned)(B * ((q_len + 7) / 8) * H), (unsigned)ns);
     hipLaunchKernelGGL((cross_attn_multi_kernel<bf16_t, 8>), gm, dim3(256), 0, s, (const bf16_t*)q, (int)q_len, (int)H,
                        (const bf16_t*)k, (const bf16_t*)v, (int)S, chunk, part, cnt, (bf16_t*)out);
-  } else if (dtype == KW_DT_BF16 && q_len == 1 && row_kernel_fits<false>(B * H, S)) {
-    CRP p{};
+  } else if (dtype == KW_DT_BF16 && q_len == 1 && row_kernel_fits<false>(g)) {
+    CRP p = cross_crp(g, L, workspace, H, k, v, out);
     p.q = (const bf16_t*)q;
-    p.kc = (const bf16_t*)k;
-    p.vc = (const bf16_t*)v;
-    p.H = (int)H, p.d = (int)(H * HD), p.S = (int)S, p.chunk = chunk, p.ns = ns, p.n_lin = 0;
-    p.err = cnt + B * q_len * H;
-    p.out = (bf16_t*)out;
-    hipLaunchKernelGGL((cross_attn_row_kernel<false, ROW_NS>), dim3((unsigned)(B * H)), dim3(256), 0, s, p);
-  } else if (dtype == KW_DT_BF16 && XA_DMA && chunk > 224 && chunk <= 256 && S - (int64_t)(ns - 1) * chunk > 224)
+    hipLaunchKernelGGL((cross_attn_row_kernel<false, ROW_NS>), dim3((unsigned)g.rows), dim3(256), 0, s, p);
+  } else if (dtype == KW_DT_BF16 && XA_DMA && g.dma_ok())
     hipLaunchKernelGGL(cross_attn_dma_kernel, grid, dim3(256), 0, s, (const bf16_t*)q, (int)q_len, (int)H,
-                       (const bf16_t*)k, (const bf16_t*)v, (int)S, chunk,
-                       (unsigned long long*)((char*)workspace + cross_granule_offset(B, q_len, H, S)),
-                       cnt + B * q_len * H, (bf16_t*)out);
+                       (const bf16_t*)k, (const bf16_t*)v, (int)S, chunk, L.at<unsigned long long>(workspace, L.wave_gran),
+                       L.at<int>(workspace, L.status), (bf16_t*)out);
   else if (dtype == KW_DT_BF16)
     hipLaunchKernelGGL(cross_attn_kernel<bf16_t>, grid, dim3(256), 0, s, (const bf16_t*)q, (int)q_len, (int)H,
                        (const bf16_t*)k, (const bf16_t*)v, (int)S, chunk, part, cnt, (bf16_t*)out);
@@ -1903,25 +1851,19 @@ extern "C" int kw_cross_attn_step(int dtype, const void* q, int64_t B, int64_t q
   return KW_OK;
 }
 
-static size_t xq_gran_offset(int64_t M, int64_t H, int64_t S) {
-  return (kw_cross_attn_workspace(M, 1, H, HD, S) + 63) & ~(size_t)63;
-}
-
+// the shapes kw_dec_xq_cross covers: the projection's rows and width, and chunks the chunk grid's key groups fit
 static bool xq_shape_ok(int64_t M, int64_t d, int64_t H, int64_t S) {
-  if (!proj_shape_ok(M, d) || H < 1 || d != HD * H || S < 1 || S > 2048) return false;
-  const int ns = cross_splits(S);
-  const int64_t chunk = (S + ns - 1) / ns;
-  return ns >= 1 && chunk > 224 && chunk <= 256 && S - (int64_t)(ns - 1) * chunk > 224;  // cross_attn_dma_kernel's
+  return proj_shape_ok(M, d) && H >= 1 && d == HD * H && S >= 1 && S <= 2048 && CrossGeo(M * H, S).dma_ok();
 }
 
 extern "C" size_t kw_dec_xq_cross_workspace(int64_t M, int64_t d, int64_t H, int64_t S) {
   if (M < 1 || d < 2 || H < 1 || S < 1) return 0;
-  return xq_gran_offset(M, H, S) + (size_t)M * (size_t)(d / 2) * sizeof(unsigned long long);
+  return CrossLayout(CrossGeo(M * H, S), M * (d / 2)).fused_end;
 }
 
 extern "C" size_t kw_dec_xq_cross_status_offset(int64_t M, int64_t d, int64_t H, int64_t S) {
   (void)d;
-  return kw_cross_attn_status_offset(M, 1, H, HD, S);  // status word, then the fault-injection word
+  return CrossLayout(CrossGeo(M * H, S)).status;  // status word, then the fault-injection word
 }
 
 extern "C" int kw_dec_xq_cross_supported(int64_t M, int64_t d, int64_t H, int64_t S) {
@@ -1934,48 +1876,22 @@ extern "C" int kw_dec_xq_cross(const kw_dec_xq_cross_args* a, kw_stream_t stream
   if (!xq_shape_ok(a->M, a->d, a->H, a->S) || (a->ldx != KW_LD_TILED && (a->ldx < a->d || a->ldx % 8)) || (uintptr_t)a->x % 16)
     return kw_set_error_msg(KW_EINVAL, "kw_dec_xq_cross: M <= 32 rows, d = 64 H <= 1280, 224 < S / chunks <= 256, "
                                        "ldx % 8 == 0, 16-B aligned x");
-  if (a->ws_bytes < kw_dec_xq_cross_workspace(a->M, a->d, a->H, a->S))
+  const CrossGeo g(a->M * a->H, a->S);
+  const CrossLayout L(g, a->M * (a->d / 2));
+  if (a->ws_bytes < L.fused_end)
     return kw_set_error_msg(KW_EINVAL, "kw_dec_xq_cross: needs a zero-filled workspace of kw_dec_xq_cross_workspace()");
-  XQP p;
-  p.x = reinterpret_cast<const bf16_t*>(a->x);
-  p.ldx = a->ldx;
-  p.ln_eps = a->ln_eps;
-  p.ln_colsum = a->ln_colsum;
-  p.W = reinterpret_cast<const bf16x8*>(a->W);
-  p.bias = a->bias;
-  p.scale = a->scale;
-  p.M = (int)a->M;
-  p.d = (int)a->d;
-  p.H = (int)a->H;
-  p.n_lin = (int)(a->d / 16);
-  p.S = (int)a->S;
-  p.ns = cross_splits(a->S);
-  p.chunk = (int)((a->S + p.ns - 1) / p.ns);
-  p.kc = reinterpret_cast<const bf16_t*>(a->k);
-  p.vc = reinterpret_cast<const bf16_t*>(a->v);
-  char* ws = reinterpret_cast<char*>(a->workspace);
-  p.qg = reinterpret_cast<unsigned long long*>(ws + xq_gran_offset(a->M, a->H, a->S));
-  p.gran = reinterpret_cast<unsigned long long*>(ws + cross_granule_offset(a->M, 1, a->H, a->S));
-  p.err = reinterpret_cast<int*>(ws + cross_partials_bytes(a->M, 1, a->H, a->S)) + a->M * a->H;
-  p.out = reinterpret_cast<bf16_t*>(a->out);
-  p.out_t = a->ldx == KW_LD_TILED ? (int)((a->M + 15) / 16) : 0;
-  if (row_kernel_fits<true>(a->M * a->H, a->S)) {  // one pair workgroup per (row, head), chunks pipelined
-    CRP r{};
-    r.qg = p.qg;
-    r.kc = p.kc;
-    r.vc = p.vc;
-    r.H = p.H, r.d = p.d, r.S = p.S, r.chunk = p.chunk, r.ns = p.ns, r.n_lin = p.n_lin;
-    r.err = p.err;
-    r.out = p.out;
-    r.out_t = p.out_t;
-    r.proj = ProjArgs{p.x, p.ldx, p.M, p.d, p.d, p.ln_eps, p.ln_colsum, p.W, p.bias, p.scale, p.d, p.err + 1};
-    hipLaunchKernelGGL((cross_attn_row_kernel<true, ROW_NS>), dim3((unsigned)(p.n_lin + a->M * a->H)), dim3(256), 0,
-                       (hipStream_t)stream, r);
-    KW_CHECK_LAUNCH();
-    return KW_OK;
-  }
-  const int64_t grid = p.n_lin + a->M * a->H * p.ns;
-  hipLaunchKernelGGL(xq_cross_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, p);
+  CRP p = cross_crp(g, L, a->workspace, a->H, a->k, a->v, a->out);
+  const int M = (int)a->M, d = (int)a->d;
+  p.qg = L.at<unsigned long long>(a->workspace, L.query_gran);
+  p.n_lin = d / 16;
+  p.out_t = a->ldx == KW_LD_TILED ? (M + 15) / 16 : 0;
+  p.proj = ProjArgs{reinterpret_cast<const bf16_t*>(a->x), a->ldx, M, d, d, a->ln_eps, a->ln_colsum,
+                    reinterpret_cast<const bf16x8*>(a->W), a->bias, a->scale, d, p.err + 1};
+  if (row_kernel_fits<true>(g))  // one pair workgroup per (row, head), chunks pipelined
+    hipLaunchKernelGGL((cross_attn_row_kernel<true, ROW_NS>), dim3((unsigned)(p.n_lin + g.rows)), dim3(256), 0,
+                       (hipStream_t)stream, p);
+  else  // the chunk grid
+    hipLaunchKernelGGL(xq_cross_kernel, dim3((unsigned)(p.n_lin + g.rows * g.ns)), dim3(256), 0, (hipStream_t)stream, p);
   KW_CHECK_LAUNCH();
   return KW_OK;
 }

@@ -38,6 +38,15 @@ __device__ __forceinline__ void unpack8(const Row8<T>& r, float v[8]) {
   }
 }
 
+// the lane's 8 query dims (16 B of the bf16 row, or the data words of its 4 query granules) in log2 units
+__device__ __forceinline__ void query_log2(const u32x4& qraw, float ql[8]) {
+  Row8<bf16_t> qr;
+  qr.u[0] = qraw;
+  unpack8<bf16_t>(qr, ql);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ql[i] *= LOG2E;
+}
+
 // bf16 decode attention, one query row over one wave's key groups j (lane (slot, sub) holds 16 B of key rows
 // slot + 32 j): scores in log2 units (the query carries log2 e, so p = exp2(s - m) is one v_exp), the wave's
 // OWN softmax reference m_w (no workgroup barrier between the scores and the values), the row sum and the 8
@@ -157,6 +166,30 @@ __device__ __forceinline__ void put_granule(unsigned long long* g, float v) {
 
 __device__ __forceinline__ unsigned long long peek_granule(const unsigned long long* g) {
   return __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// The query hand-off of the fused projection + cross-attention launches: g holds the lane's 4 {bf16 x 2, tag}
+// query granules q4[0..3] as first loaded; they are polled until every lane of the wave holds tag 1.  A poll that
+// outlasts XG_SPIN_LIMIT rounds (the projection never published: a protocol failure) raises the error word and
+// substitutes bf16 NaN pairs, so the row fails loudly.  Returns the 4 data words (the lane's 16 B of the query row).
+__device__ __forceinline__ u32x4 wait_query_granules(const unsigned long long* q4, unsigned long long (&g)[4], int* err) {
+  bool ok = ((g[0] & g[1] & g[2] & g[3]) >> 32) == 1ull;
+  for (int it = 0; __builtin_amdgcn_ballot_w64(!ok) != 0; ++it) {  // the projection not yet published: poll
+    if (it >= XG_SPIN_LIMIT) {
+      if (!ok) {
+        __hip_atomic_store(err, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+#pragma unroll
+        for (int i = 0; i < 4; ++i) g[i] = 0x7fc07fc0ull | (1ull << 32);
+        ok = true;
+      }
+      continue;
+    }
+    __builtin_amdgcn_s_sleep(KW_POLL_SLEEP);
+#pragma unroll
+    for (int i = 0; i < 4; ++i) g[i] = peek_granule(q4 + i);
+    ok = ((g[0] & g[1] & g[2] & g[3]) >> 32) == 1ull;
+  }
+  return u32x4{(uint32_t)g[0], (uint32_t)g[1], (uint32_t)g[2], (uint32_t)g[3]};
 }
 
 }  // namespace

@@ -1,4 +1,4 @@
-// C-ABI bookkeeping: version and per-thread error message (include/kwhisper.h).
+// C-ABI bookkeeping: version and per-thread error message (include/kwhisper.h); the device's CU count for the launchers.
 #include <stdio.h>
 #include <string.h>
 
@@ -14,6 +14,16 @@ int kw_set_error(hipError_t e) {
 int kw_set_error_msg(int code, const char* msg) {
   snprintf(g_err, sizeof(g_err), "%s", msg);
   return code;
+}
+
+int kw_device_cus() {
+  static const int ncu = [] {
+    int dev = 0, n = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess)
+      return 0;
+    return n > 0 ? n : 0;
+  }();
+  return ncu;
 }
 
 extern "C" int kw_version(void) { return 112; }

@@ -38,11 +38,6 @@
 
 namespace {
 
-__device__ __forceinline__ void glds16(const void* g, char* lds_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
-}
-
 constexpr int CNT_MAX = 4096;  // seam arrival counters at the start of the workspace
 constexpr int MAXW = 8;        // waves per workgroup
 constexpr int KSMAX = 8;       // K splits per column group (host-checked)
@@ -793,8 +788,7 @@ __device__ __forceinline__ bf16x8 lmr_lds_read(const char* p) {
   // inline asm: a builtin LDS read after an LDS-DMA would get an s_waitcnt vmcnt(0) (the compiler
   // cannot tell the slice being read from the ones in flight); lmr waits are explicit lgkmcnt counts
   bf16x8 v;
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"((uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p)
-               : "memory");
+  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_u32(p)) : "memory");
   return v;
 }
 __device__ __forceinline__ void lmr_barrier() {  // raw s_barrier: no implicit vmcnt(0) drain
@@ -1347,14 +1341,8 @@ size_t x_lds_bytes_rows(int tiles, int rows, bool xlds) {
 }
 
 int device_cus() {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        ncu <= 0)
-      ncu = 256;
-  }
-  return ncu;
+  const int ncu = kw_device_cus();
+  return ncu ? ncu : 256;
 }
 
 template <int KTM, int NCB, bool LNA, int EPI, typename TC, bool H2>
@@ -1411,13 +1399,7 @@ hipError_t launch(const DecP& p, bool resid, const Geo& g, bool c_f32, hipStream
 
 // the LM head's column groups per workgroup: one run per CU
 int lmh_groups_per_wg(int64_t N) {
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        ncu <= 0)
-      ncu = 256;
-  }
+  const int ncu = device_cus();
   const int groups = (int)((N + 16 * LMH_NCB - 1) / (16 * LMH_NCB));
   return (groups + ncu - 1) / ncu;
 }
@@ -1436,6 +1418,34 @@ int lmg_grid(int64_t N) {
   return (groups + per - 1) / per;
 }
 constexpr int LMG_MAXG = 256;  // workgroups whose partials the last arriver merges (16 per lane)
+
+// The launch descriptor of all a->M rows, as the arguments give it; a caller that launches a window of the rows, or
+// uses the split-K workspace, sets those fields (and xlds / vec_epi, which depend on the geometry) itself.
+DecP decp_from_args(const kw_dec_linear_args* a) {
+  DecP p{};
+  p.x = reinterpret_cast<const bf16_t*>(a->x);
+  p.ldx = a->ldx;
+  p.ln = a->ln;
+  p.ln_eps = a->ln_eps;
+  p.ln_colsum = a->ln_colsum;
+  p.W = reinterpret_cast<const bf16x8*>(a->W);
+  p.bias = a->bias;
+  p.C = a->C;
+  p.ldc = a->ldc;
+  p.gelu = a->gelu;
+  p.scale = a->scale;
+  p.scale_cols = (int)a->scale_cols;
+  p.h = a->h;
+  p.hb = reinterpret_cast<bf16_t*>(a->hb);
+  p.ldh = a->ldh;
+  p.M = (int)a->M;
+  p.N = (int)a->N;
+  p.K = (int)a->K;
+  const int tiles = (int)((a->M + 15) / 16);
+  p.xt = a->ldx == KW_LD_TILED ? tiles : 0;
+  p.hbt = (a->epilogue & KW_EPI_HB_TILED) ? tiles : 0;
+  return p;
+}
 
 }  // namespace
 
@@ -1465,20 +1475,7 @@ extern "C" int kw_dec_lm_greedy(const kw_dec_linear_args* a, const kw_sampler_ar
     return kw_set_error_msg(KW_EUNSUPPORTED, "kw_dec_lm_greedy: shape not covered (kw_dec_lm_greedy_supported)");
   if (g->ws_bytes < kw_dec_lm_greedy_workspace(a->M, a->N) || (uintptr_t)g->workspace % 16 != 0)
     return kw_set_error_msg(KW_EINVAL, "kw_dec_lm_greedy: needs a zero-filled workspace of kw_dec_lm_greedy_workspace()");
-  DecP p{};
-  p.x = reinterpret_cast<const bf16_t*>(a->x);
-  p.ldx = a->ldx;
-  p.ln = 1;
-  p.ln_eps = a->ln_eps;
-  p.ln_colsum = a->ln_colsum;
-  p.W = reinterpret_cast<const bf16x8*>(a->W);
-  p.bias = a->bias;
-  p.C = a->C;
-  p.ldc = a->ldc;
-  p.M = (int)a->M;
-  p.N = (int)a->N;
-  p.K = (int)a->K;
-  p.xt = a->ldx == KW_LD_TILED ? (int)((a->M + 15) / 16) : 0;  // (M <= 32: kw_dec_lm_greedy_supported)
+  const DecP p = decp_from_args(a);  // (a fragment-major x: M <= 32, kw_dec_lm_greedy_supported)
   LmGreedy sg{};
   sg.mask = g->suppress_mask;
   sg.bsup = g->begin_suppress;
@@ -1548,19 +1545,7 @@ extern "C" int kw_dec_linear(const kw_dec_linear_args* a, kw_stream_t stream) {
   if (xtiled && (a->M > 32 || (lm_shape && !lmh_fits(a->M, a->N, nkt))))
     return kw_set_error_msg(KW_EINVAL, "kw_dec_linear: a KW_LD_TILED x needs M <= 32 (LM head: a shape lm_head_kernel covers)");
   if (lm_shape && a->M > LMH_MAX_ROWS && a->M <= LMR_MAXROWS && nkt % 8 == 0) {
-    DecP p{};
-    p.x = reinterpret_cast<const bf16_t*>(a->x);
-    p.ldx = a->ldx;
-    p.ln = 1;
-    p.ln_eps = a->ln_eps;
-    p.ln_colsum = a->ln_colsum;
-    p.W = reinterpret_cast<const bf16x8*>(a->W);
-    p.bias = a->bias;
-    p.C = a->C;
-    p.ldc = a->ldc;
-    p.M = (int)a->M;
-    p.N = (int)a->N;
-    p.K = (int)a->K;
+    const DecP p = decp_from_args(a);
     const int n_cb = (int)((a->N + 15) / 16);
     // eight 16-column waves per workgroup, four k-tile slices staged ahead (one workgroup per CU); a slice holds
     // 128 G rows, G = ceil(M / 128)
@@ -1577,30 +1562,15 @@ extern "C" int kw_dec_linear(const kw_dec_linear_args* a, kw_stream_t stream) {
   // rows: one launch with a grid z-slice per 32-row chunk (K-split launches: up to ZMAX chunks each)
   const int64_t step = (g.ks == 1 || lmh) ? a->M : 32 * ZMAX;
   for (int64_t m0 = 0; m0 < a->M; m0 += step) {
-    DecP p;
+    DecP p = decp_from_args(a);  // rows [m0, m0 + step) of it
     p.M = (int)(a->M - m0 < step ? a->M - m0 : step);
-    p.N = (int)a->N;
-    p.K = (int)a->K;
-    p.x = reinterpret_cast<const bf16_t*>(a->x) + m0 * a->ldx;
-    p.ldx = a->ldx;
-    p.ln = a->ln;
-    p.ln_eps = a->ln_eps;
-    p.ln_colsum = a->ln_colsum;
-    p.W = reinterpret_cast<const bf16x8*>(a->W);
-    p.bias = a->bias;
+    p.x += m0 * a->ldx;
     const size_t csz = a->c_dtype == KW_DT_F32 ? 4 : 2;
-    p.C = a->C ? reinterpret_cast<char*>(a->C) + m0 * a->ldc * csz : nullptr;
-    p.ldc = a->ldc;
-    p.gelu = a->gelu;
-    p.scale = a->scale;
-    p.scale_cols = (int)a->scale_cols;
-    p.h = a->h ? a->h + m0 * a->ldh : nullptr;
-    p.hb = a->hb ? reinterpret_cast<bf16_t*>(a->hb) + m0 * a->ldh : nullptr;
-    p.ldh = a->ldh;
+    if (p.C) p.C = reinterpret_cast<char*>(p.C) + m0 * a->ldc * csz;
+    if (p.h) p.h += m0 * a->ldh;
+    if (p.hb) p.hb += m0 * a->ldh;
     p.cnt = reinterpret_cast<int*>(a->workspace);
     p.slab = a->workspace ? reinterpret_cast<float*>(reinterpret_cast<char*>(a->workspace) + CNT_MAX * sizeof(int)) : nullptr;
-    p.xt = xtiled ? (int)((a->M + 15) / 16) : 0;
-    p.hbt = hbtiled ? (int)((a->M + 15) / 16) : 0;
     p.xlds = !xtiled && use_xlds(a->N, g) ? 1 : 0;
     // 16-B epilogue pieces: whole 16-column blocks and 16-B aligned rows (every z-chunk's rows too)
     p.vec_epi = a->N % 16 == 0 &&

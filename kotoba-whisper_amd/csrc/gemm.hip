@@ -35,11 +35,6 @@ constexpr int BM = 128, BN = 128, BK = 64;
 constexpr int STAGE_BYTES = (BM + BN) * BK * 2;  // 32 KB
 constexpr int GEMM_LDS = 2 * STAGE_BYTES;       // 64 KB
 
-__device__ __forceinline__ void glds16(const void* g, char* lds_base) {
-  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
-                                   (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
-}
-
 template <int EPI, typename TC>
 __global__ __launch_bounds__(256, 2) void gemm_bf16_kernel(GemmP p) {
   extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -170,22 +165,11 @@ constexpr int P_LDS_ALLOC = P_LDS + 8 * P_EPI + P_BIAS;  // 147.5 KB
 // in-flight LDS-DMA targets and would put an s_waitcnt vmcnt(0) -- which also waits for every store
 // already issued -- in front of each one, serialising the store stream.  The staging region never
 // receives LDS-DMA, so only the wave's own ds_writes (in order) must precede the reads.
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
-}
 // issue one 16-B staging read; lds_wait(v) (s_waitcnt lgkmcnt(0) tied to v) must precede any use of v
 __device__ __forceinline__ void lds_issue_read(const float* p, f32x4& v) {
-  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_addr(p)) : "memory");
+  asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_u32(p)) : "memory");
 }
 __device__ __forceinline__ void lds_wait(f32x4& v) { asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v)); }
-
-__device__ __forceinline__ void pp_barrier() {
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_sched_barrier(0);
-  __builtin_amdgcn_s_barrier();
-  __builtin_amdgcn_sched_barrier(0);
-  asm volatile("" ::: "memory");
-}
 
 template <int EPI, typename TC>
 __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
@@ -334,8 +318,8 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
     // hoisted out of the tile loop (they would stay live across the main loop and spill)
     int ln = lane;
     asm volatile("" : "+v"(ln));
-    pp_barrier();
-    if (grp == 1) pp_barrier();  // the stagger
+    raw_barrier();
+    if (grp == 1) raw_barrier();  // the stagger
 #pragma unroll
     for (int i = 0; i < 8; ++i)
 #pragma unroll
@@ -347,12 +331,12 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
         const int buf = t & 1;
         read_stage(buf, t + 1, t + 1 < nk);  // + A of tile t+1 (its buffer's last reader finished in slot 2t-1)
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        pp_barrier();
+        raw_barrier();
         mma();
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // A of tile t+1 landed
-        pp_barrier();
+        raw_barrier();
       }
-      pp_barrier();  // balances group 1's stagger barrier
+      raw_barrier();  // balances group 1's stagger barrier
     } else {
       // group 1 stages W of tile t+2 in its own read slot, after its reads of tile t drained: group 0 read
       // tile t one slot earlier, so the buffer is free; the W of tile t+1 (issued one read slot earlier)
@@ -367,9 +351,9 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
         } else {
           asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         }
-        pp_barrier();
+        raw_barrier();
         mma();
-        pp_barrier();
+        raw_barrier();
       }
     }
     // every wave passed the last barrier: the K-tile buffers are free, every glds retired.  Pull this
@@ -393,7 +377,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
     const bool more = pos < run_len;
     if (more && overlap) {
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      pp_barrier();  // every wave holds its bias before wave 0 restages the bias row
+      raw_barrier();  // every wave holds its bias before wave 0 restages the bias row
       set_tile(pos, ln);
       prologue();
     }
@@ -559,7 +543,7 @@ __global__ __launch_bounds__(512) void gemm256_kernel(GemmP p) {
       prologue_wait(full);
     } else {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      pp_barrier();  // every wave read its bias
+      raw_barrier();  // every wave read its bias
       set_tile(pos, ln);
       prologue();
       prologue_wait(false);
@@ -635,13 +619,7 @@ hipError_t launch256_one(const GemmP& p, hipStream_t s) {
     if (e != hipSuccess) return e;
     attr = true;
   }
-  static int ncu = 0;
-  if (!ncu) {
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
-        ncu <= 0)
-      ncu = 256;
-  }
+  const int ncu = kw_device_cus() ? kw_device_cus() : 256;
   const int nwg = ((p.M + PB - 1) / PB) * (p.N / PB);
   const int grid = nwg < ncu ? nwg : ncu;  // persistent: one 147.5-KB-LDS workgroup per CU
   hipLaunchKernelGGL((gemm256_kernel<EPI, TC>), dim3(grid), dim3(512), P_LDS_ALLOC, s, p);

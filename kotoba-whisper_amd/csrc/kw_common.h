@@ -41,6 +41,31 @@ __device__ __forceinline__ int64_t kw_tiled_off(int m, int n, int T) {
   return ((int64_t)((n >> 5) * T + (m >> 4)) * 64 + (m & 15) + 16 * ((n & 31) >> 3)) * 8 + (n & 7);
 }
 
+// the 32-bit LDS address of a __shared__ pointer (inline-asm ds_read operands)
+__device__ __forceinline__ uint32_t lds_u32(const void* p) {
+  return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
+}
+
+// 16 B per lane global -> LDS by LDS-DMA (global_load_lds_dwordx4); _nt: non-temporal (streamed once)
+__device__ __forceinline__ void glds16(const void* g, char* lds_base) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                   (__attribute__((address_space(3))) void*)lds_base, 16, 0, 0);
+}
+__device__ __forceinline__ void glds16_nt(const void* g, char* lds_base) {
+  __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)g,
+                                   (__attribute__((address_space(3))) void*)lds_base, 16, 0, 2);
+}
+
+// a workgroup barrier without __syncthreads()'s fence (which waits vmcnt(0), draining loads still in flight);
+// compiler barriers on both sides keep every memory access (LDS reads of DMA'd data) on its side
+__device__ __forceinline__ void raw_barrier() {
+  asm volatile("" ::: "memory");
+  __builtin_amdgcn_sched_barrier(0);
+  __builtin_amdgcn_s_barrier();
+  __builtin_amdgcn_sched_barrier(0);
+  asm volatile("" ::: "memory");
+}
+
 template <typename T> struct TypeIO;
 template <> struct TypeIO<float> {
   static __device__ __forceinline__ float ld(const float* p) { return *p; }
@@ -134,3 +159,4 @@ __device__ __forceinline__ float wave_max(float v) {
 
 int kw_set_error(hipError_t e);
 int kw_set_error_msg(int code, const char* msg);
+int kw_device_cus();  // compute units of the current device (queried once); 0 when the query fails

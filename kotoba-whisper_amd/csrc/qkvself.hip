@@ -30,7 +30,6 @@
 
 namespace {
 
-constexpr int QS_SPIN_LIMIT = 1 << 22;
 constexpr int QS_PAIRS = 2;      // (row, head) pairs per attention workgroup, two waves each
 constexpr int QS_MAX_LEN = 256;  // key positions per step: two 128-key passes
 
@@ -102,7 +101,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void q
     int it = 0;
     for (;; ++it) {
       x = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if ((x >> 32) == 1ull || it >= QS_SPIN_LIMIT) break;
+      if ((x >> 32) == 1ull || it >= XG_SPIN_LIMIT) break;
       __builtin_amdgcn_s_sleep(KW_POLL_SLEEP);
     }
     if ((x >> 32) != 1ull || !len_ok) {
@@ -120,13 +119,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void q
     const u32x4 knew = {st[32 + sub * 4], st[32 + sub * 4 + 1], st[32 + sub * 4 + 2], st[32 + sub * 4 + 3]};
     const u32x4 vnew = {st[64 + sub * 4], st[64 + sub * 4 + 1], st[64 + sub * 4 + 2], st[64 + sub * 4 + 3]};
     float ql[8];
-    {
-      Row8<bf16_t> qr;
-      qr.u[0] = qraw;
-      unpack8<bf16_t>(qr, ql);
-#pragma unroll
-      for (int i = 0; i < 8; ++i) ql[i] *= LOG2E;
-    }
+    query_log2(qraw, ql);
     const int pn = p0 >> 7, jn = (p0 & 127) >> 4, sn = p0 & 15;
 #pragma unroll
     for (int j = 0; j < 8; ++j)

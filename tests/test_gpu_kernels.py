@@ -993,6 +993,71 @@ def test_xq_cross_fused_matches_two_launches(M, d, H, S):
     assert err1 < 2e-2, err1
 
 
+def _rearm_through_changing_inputs(launch, ws_bytes, inputs):
+    """``launch(x, ws)`` -> output, once per input on ONE zero-filled workspace: each output equals, bit for bit, the
+    same input's on a fresh zero-filled workspace (nothing of an earlier launch -- a query or chunk-partial granule, a
+    tag -- is read by a later one), and the shared workspace is all zero again after the last launch."""
+    ws = torch.zeros(ws_bytes // 4 + 1, device="cuda")
+    got = [launch(x, ws).clone() for x in inputs]
+    torch.cuda.synchronize()
+    assert int(ws.view(torch.int32).abs().sum()) == 0, "workspace not re-armed / status word set"
+    assert not torch.equal(got[0], got[1]) and not torch.equal(got[1], got[2])  # (the inputs do differ)
+    for i, x in enumerate(inputs):
+        fresh = launch(x, torch.zeros(ws_bytes // 4 + 1, device="cuda"))
+        assert not bool(torch.isnan(fresh.float()).any())
+        assert torch.equal(got[i], fresh), i
+
+
+@pytest.mark.parametrize("S", [1500, 256])  # six chunks (granule combine) / one chunk (no combine)
+@pytest.mark.parametrize("B,H", [(1, 6), (17, 6)])
+def test_cross_attn_step_rearms_between_different_inputs(B, H, S):
+    """kw_cross_attn_step (bf16, q_len 1) on the chunk grid (cross_attn_dma_kernel: B H is below the CU count), three
+    launches with three different (q, K, V) on one workspace."""
+    assert not ops.cross_attn_pair_kernel(B * H, S)
+    d = H * 64
+    g = torch.Generator(device="cuda").manual_seed(B * 10000 + S)
+    inputs = [((torch.randn(B, d, device="cuda", generator=g) * 0.3).bfloat16(),
+               torch.randn(B, H, S, 64, device="cuda", generator=g).bfloat16(),
+               torch.randn(B, H, S, 64, device="cuda", generator=g).bfloat16()) for _ in range(3)]
+
+    def launch(x, ws):
+        q, k, v = x
+        out = torch.full((B, d), 7.0, device="cuda", dtype=torch.bfloat16)
+        ops.cross_attn_step(q, B, 1, H, 64, k, v, S, out, ws)
+        return out
+
+    _rearm_through_changing_inputs(launch, ops.cross_attn_workspace_bytes(B, 1, H, 64, S), inputs)
+
+
+@pytest.mark.parametrize("tiled", [False, True])
+@pytest.mark.parametrize("S", [1500, 256])
+@pytest.mark.parametrize("M,d,H", [(1, 384, 6), (17, 384, 6)])
+def test_xq_cross_rearms_between_different_inputs(M, d, H, S, tiled):
+    """kw_dec_xq_cross on the chunk grid (xq_cross_kernel), row-major and KW_LD_TILED: three launches with three
+    different (hb, K, V) on one workspace -- the query granules and the chunk-partial granules are both re-armed."""
+    assert not ops.cross_attn_pair_kernel(M * H, S, fused=True)
+    assert ops.xq_cross_supported(M, d, H, S)
+    g = torch.Generator(device="cuda").manual_seed(M * 10000 + S + int(tiled))
+    W = (torch.randn(d, d, device="cuda", generator=g) / d ** 0.5).bfloat16()
+    packed, colsum = ops.pack_weight(W), ops.ln_colsum(W)
+    bias = torch.randn(d, device="cuda", generator=g) * 0.1
+    rows = 16 * ((M + 15) // 16)
+
+    def make():
+        hb = torch.randn(rows if tiled else M, d, device="cuda", generator=g).bfloat16()
+        return (ops.act_tile(hb) if tiled else hb, torch.randn(M, H, S, 64, device="cuda", generator=g).bfloat16(),
+                torch.randn(M, H, S, 64, device="cuda", generator=g).bfloat16())
+
+    def launch(x, ws):
+        hb, k, v = x
+        out = torch.full((rows if tiled else M, d), 7.0, device="cuda", dtype=torch.bfloat16)
+        ops.XqCrossPlan(hb, packed, M, d, H, ln=(1e-5, colsum), bias=bias, scale=0.125, k=k, v=v, S=S, out=out,
+                        workspace=ws, ldx=ops.KW_LD_TILED if tiled else None)()
+        return out
+
+    _rearm_through_changing_inputs(launch, ops.xq_cross_workspace_bytes(M, d, H, S), [make() for _ in range(3)])
+
+
 def test_xq_cross_rejects_what_it_does_not_cover():
     assert not ops.xq_cross_supported(33, 1280, 20, 1500)  # more rows than one 32-row tile
     assert not ops.xq_cross_supported(4, 1280, 16, 1500)   # head_dim != 64

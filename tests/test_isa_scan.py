@@ -28,6 +28,8 @@ CASES = {
         (r"self_attn_step1ItLb0E", 19),
         (r"self_attn_step1ItLb1E", 27),
         (r"cross_attn_dma_kernel", 17),
+        # the same body behind the in-launch query hand-off: 4 query granule loads + 8 K pieces + 8 V rows
+        (r"xq_cross_kernel", 20),
         (r"cross_attn_multi_kernelItLi4E", 20),  # 4 query rows + 8 K + 8 V rows
         (r"cross_attn_mfma_kernel", 20),
     ],
