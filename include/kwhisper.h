@@ -321,7 +321,9 @@ size_t kw_greedy_step_workspace(int64_t B);
  *       NULL to skip storing them (the greedy step needs only the arg-max);
  *   g:  a kw_sampler_args of the same B x V with return_timestamps = 0 and scores_out = NULL; g->logits and
  *       g->counter are not used; g->workspace >= kw_dec_lm_greedy_workspace(B, V) bytes, ZERO-FILLED before first
- *       use (every launch re-arms it).
+ *       use (every launch re-arms it); g->max_length - g->begin_index <= 448: the launch looks for a row's earlier
+ *       EOS in the 448 positions after begin_index only, so a longer generation is KW_EUNSUPPORTED (kw_greedy_step
+ *       scans every position up to cur_len).
  * kw_dec_lm_greedy_supported(B, V, d): 1 when the shape is covered (else use kw_dec_linear + kw_greedy_step). */
 int kw_dec_lm_greedy(const kw_dec_linear_args* lm, const kw_sampler_args* g, kw_stream_t stream);
 size_t kw_dec_lm_greedy_workspace(int64_t B, int64_t V);

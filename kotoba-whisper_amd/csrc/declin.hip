@@ -22,11 +22,15 @@
 //    (W' = W diag(gamma), b' = b + W beta) and colsum(W') is precomputed per column;
 //  * RESID epilogue: h(f32) += acc + bias, plus the bf16 mirror hb = h (the next LayerNorm's operand).
 // Everything is bitwise deterministic: no float atomics, every reduction in a fixed order.
+// The tile steps every kernel here shares (fragment loads, the MFMA loop, the LayerNorm statistics and their fold) are
+// in declin_tile.h, the epilogue steps (epi_value, load_resid, store_block16, tile_job_epilogue) below: a kernel
+// composes them, it does not copy them -- the kernels' bitwise equalities rest on that.
 #include <stdio.h>
 #include <stdlib.h>
 
 #include <algorithm>
 
+#include "declin_tile.h"
 #include "kw_common.h"
 
 // development hooks (tools/lab/declin_lab.hip records s_memrealtime stamps through them); no-ops here
@@ -69,16 +73,49 @@ struct DecP {
   int hbt;      // RESID: hb is written fragment-major (KW_EPI_HB_TILED) with hbt row tiles; 0: row-major [M][ldh]
 };
 
+// The descriptor of rows [m0, m0 + rows) of p0's M (fewer at the end): x, C (csz bytes per element), h and hb advanced
+// to row m0.  A fragment-major x / hb steps by whole 16-row tiles (m0 % 16 == 0: the next row tile lies 512 elements
+// on) and keeps its tile count
+__host__ __device__ __forceinline__ DecP rows_window(const DecP& p0, int m0, int rows, size_t csz) {
+  DecP p = p0;
+  p.M = rows < p0.M - m0 ? rows : p0.M - m0;
+  if (m0) {
+    p.x += p0.xt ? (int64_t)m0 * 32 : m0 * p0.ldx;
+    if (p.C) p.C = reinterpret_cast<char*>(p.C) + (int64_t)m0 * p0.ldc * csz;
+    if (p.h) p.h += m0 * p0.ldh;
+    if (p.hb) p.hb += p0.hbt ? (int64_t)m0 * 32 : m0 * p0.ldh;
+  }
+  return p;
+}
+
 // hb's element (m, n): the bf16 residual mirror, row-major or fragment-major
 __device__ __forceinline__ bf16_t* hb_at(const DecP& p, int m, int n) {
   return p.hb + (p.hbt ? kw_tiled_off(m, n, p.hbt) : (int64_t)m * p.ldh + n);
 }
 
+// One wave's 16 x 16 output block (the MFMA C layout, as store_block16) stored element by element; rows >= M and
+// columns >= N are not stored.  TH: hb may be fragment-major (p.hbt)
+template <int EPI, typename TC, bool TH>
+__device__ __forceinline__ void store_elems(const DecP& p, const float (&v4)[4], int mb, int M, int nb, int lane) {
+  const int n = nb + (lane & 15);
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int m = mb + 4 * (lane >> 4) + r;
+    if (n >= p.N || m >= M) continue;
+    if constexpr (EPI == KW_EPI_RESID) {
+      p.h[(int64_t)m * p.ldh + n] = v4[r];
+      *(TH ? hb_at(p, m, n) : p.hb + (int64_t)m * p.ldh + n) = f2bf(v4[r]);
+    } else {
+      TypeIO<TC>::st(reinterpret_cast<TC*>(p.C) + (int64_t)m * p.ldc + n, v4[r]);
+    }
+  }
+}
+
 // One wave's 16 x 16 output block: lane holds rows mb + 4 (lane / 16) + r (r < 4) of column nb + lane % 16 (the MFMA C
 // layout).  vec (DecP::vec_epi): staged row-major in stg (the wave's own 16 x 20 floats of LDS) and stored as whole
-// 16-B pieces -- f32 rows of 4 columns (one per lane), bf16 rows of 8 (lanes 0..31) -- otherwise element by element;
-// rows >= M and columns >= N are not stored.  RESID: h (f32) and its bf16 mirror hb; STORE: C of TC.  r06: the
-// element stores wrote 16 columns x 4 rows of 2-4-B pieces per instruction.
+// 16-B pieces -- f32 rows of 4 columns (one per lane), bf16 rows of 8 (lanes 0..31) -- otherwise element by element
+// (store_elems); rows >= M and columns >= N are not stored.  RESID: h (f32) and its bf16 mirror hb; STORE: C of TC.
+// r06: the element stores wrote 16 columns x 4 rows of 2-4-B pieces per instruction.
 // TH: hb may be fragment-major (p.hbt; dec_linear_kernel only -- the rows kernel's stores stay as they were)
 template <int EPI, typename TC, bool TH = false>
 __device__ __forceinline__ void store_block16(const DecP& p, float (*stg)[20], const float (&v4)[4], int mb, int M,
@@ -86,9 +123,7 @@ __device__ __forceinline__ void store_block16(const DecP& p, float (*stg)[20], c
   if (p.vec_epi) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) stg[4 * (lane >> 4) + r][lane & 15] = v4[r];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     constexpr bool F32 = EPI == KW_EPI_RESID || sizeof(TC) == 4, BF16 = EPI == KW_EPI_RESID || sizeof(TC) == 2;
     if constexpr (F32) {
       float* dst = EPI == KW_EPI_RESID ? p.h : reinterpret_cast<float*>(p.C);
@@ -110,19 +145,72 @@ __device__ __forceinline__ void store_block16(const DecP& p, float (*stg)[20], c
       }
     }
   } else {
-    const int n = nb + (lane & 15);
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int m = mb + 4 * (lane >> 4) + r;
-      if (n >= p.N || m >= M) continue;
-      if constexpr (EPI == KW_EPI_RESID) {
-        p.h[(int64_t)m * p.ldh + n] = v4[r];
-        *(TH ? hb_at(p, m, n) : p.hb + (int64_t)m * p.ldh + n) = f2bf(v4[r]);
-      } else {
-        TypeIO<TC>::st(reinterpret_cast<TC*>(p.C) + (int64_t)m * p.ldc + n, v4[r]);
-      }
-    }
+    store_elems<EPI, TC, TH>(p, v4, mb, M, nb, lane);
   }
+}
+
+// The epilogue value of accumulator element v at (row with statistics ms = (mean, rstd), column n): the folded
+// LayerNorm, bias bn, then the residual hv (RESID) or GELU / scale (STORE)
+template <bool LNA, int EPI, typename TC>
+__device__ __forceinline__ float epi_value(const DecP& p, float v, const float* ms, int n, float cs, float bn, float hv) {
+  if constexpr (LNA) v = ln_fold(v, ms[0], ms[1], cs);  // LN(x) W'^T
+  v += bn;
+  if constexpr (EPI == KW_EPI_RESID) {
+    v += hv;
+  } else {
+    if (p.gelu) v = sizeof(TC) == 2 ? gelu_bf16out(v) : gelu_erf(v);
+    if (n < p.scale_cols) v *= p.scale;
+  }
+  return v;
+}
+
+// The residual rows of the tile at row m0 (lane <-> column lane & 15 of each column block, rows 4 (lane >> 4) + r of
+// each of the HH row halves, clamped to M - 1), for the (column block, row half) jobs that job(c, hh) selects
+template <int NCB, int HH, typename Job>
+__device__ __forceinline__ void load_resid(const DecP& p, int m0, int M, int cg, int lane, float (&hold)[NCB][2][4], Job job) {
+#pragma unroll
+  for (int c = 0; c < NCB; ++c) {
+    const int n = min((cg * NCB + c) * 16 + (lane & 15), p.N - 1);
+#pragma unroll
+    for (int hh = 0; hh < HH; ++hh)
+      if (job(c, hh)) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+          const int m = min(16 * hh + 4 * (lane >> 4) + r, M - 1);
+          hold[c][hh][r] = p.h[(int64_t)(m0 + m) * p.ldh + n];
+        }
+      }
+  }
+}
+struct EveryJob {
+  __device__ bool operator()(int, int) const { return true; }
+};
+
+// One (column block cj, row half hj) job of a tile's spread epilogue, on one wave: its 16 x 16 partial tiles summed in
+// wave order, its row half's LayerNorm statistics formed by the wave itself (LDS is in order within a wave; two jobs of
+// one half write the same values), the epilogue values, store_block16 -- bitwise wave 0 alone doing every job.
+// bn / cs / hv: the job's bias, column sum and residual values; the tile's rows start at m0, M of them; reduced: a
+// hook called once the sums are formed (a development stamp)
+template <int NCB, bool LNA, int EPI, typename TC, bool TH, typename Hook>
+__device__ __forceinline__ void tile_job_epilogue(const DecP& p, const f32x4 (*red)[NCB][2][64], const float (*rpart)[32][2],
+                                                  float (*rstat)[2], float (*stg)[20], int nw, int cj, int hj, float bn,
+                                                  float cs, const float (&hv)[4], int m0, int M, int nb, int lane,
+                                                  Hook reduced) {
+  if constexpr (LNA) {
+    if (lane < 16) ln_finish_row(rpart, nw, 16 * hj + lane, p.K, p.ln_eps, rstat);
+    wave_lds_sync();
+  }
+  f32x4 acc = red[0][cj][hj][lane];
+  for (int w2 = 1; w2 < nw; ++w2) acc += red[w2][cj][hj][lane];
+  reduced();
+  const int n = nb + (lane & 15);
+  float v4[4];
+#pragma unroll
+  for (int r = 0; r < 4; ++r) {
+    const int m = 16 * hj + 4 * (lane >> 4) + r;
+    v4[r] = epi_value<LNA, EPI, TC>(p, acc[r], rstat[m], n, cs, bn, hv[r]);
+  }
+  store_block16<EPI, TC, TH>(p, stg, v4, m0 + 16 * hj, m0 + M, nb, lane);
 }
 
 // H2: the second 16-row half of the tile exists (false: a row-split chunk of <= 16 rows -- its a1 / c1 / LayerNorm
@@ -152,28 +240,14 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
   // same weight slice, so it is loaded with the default policy and the second read can hit that XCD's L2; r04's nt
   // loads fetched 1.23x the o / xo weights from memory, profiles/r04p_pmc_fetch.csv)
   bf16x8 w[NCB][KTM], a0[KTM], a1[KTM];
-#pragma unroll
-  for (int c = 0; c < NCB; ++c)
-#pragma unroll
-    for (int u = 0; u < KTM; ++u) {
-      const bf16x8* src = p.W + ((int64_t)(cg * NCB + c) * nkt + min(kt0 + u, ktl)) * 64 + lane;
-      w[c][u] = H2 ? __builtin_nontemporal_load(src) : *src;
-    }
+  load_w_frags<KTM, NCB, H2>(p.W, cg, nkt, kt0, ktl, lane, w);
   const int wkt0 = (nkt * ks) / ksn, wkt1 = (nkt * (ks + 1)) / ksn;  // this workgroup's k-tiles
   const int cpr = (wkt1 - wkt0) * 4, cprp = cpr + 1;
   const bool xlds = p.xlds;
-  // fragment-major x (p.xt row tiles): a (k-tile, row half) fragment is one contiguous 1-KB piece, loaded straight
-  // into registers with the weights -- no LDS image, no barrier, no row clamp (a missing second tile re-reads the
-  // first: its output rows are >= M)
+  // fragment-major x (p.xt row tiles): the fragments are loaded straight into registers with the weights -- no LDS
+  // image, no barrier
   if (p.xt) {
-    const bf16x8* xf = reinterpret_cast<const bf16x8*>(p.x) + lane;
-    const int t1 = p.xt > 1 ? 64 : 0;
-#pragma unroll
-    for (int u = 0; u < KTM; ++u) {
-      const bf16x8* f = xf + (int64_t)(min(kt0 + u, ktl) * p.xt) * 64;
-      a0[u] = *f;
-      if constexpr (H2) a1[u] = f[t1];
-    }
+    load_x_frags_tiled<KTM, H2>(p.x, p.xt, kt0, ktl, lane, a0, a1);
   } else if (xlds) {
     // <= 16 rows: only the pieces of rows 0..15 (the second row half's fragments then hold stale LDS, and its
     // output rows -- all >= M -- are discarded; every row of an MFMA tile is independent of the others)
@@ -206,19 +280,7 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
     ecsum[c] = LNA ? p.ln_colsum[n] : 0.f;
   }
   if constexpr (EPI == KW_EPI_RESID) {
-    if (spread ? wave < J : wave == 0) {
-#pragma unroll
-      for (int c = 0; c < NCB; ++c) {
-        const int n = min((cg * NCB + c) * 16 + (lane & 15), p.N - 1);
-#pragma unroll
-        for (int hh = 0; hh < (H2 ? 2 : 1); ++hh)
-#pragma unroll
-          for (int r = 0; r < 4; ++r) {
-            const int m = min(16 * hh + 4 * (lane >> 4) + r, M - 1);
-            hold[c][hh][r] = p.h[(int64_t)m * p.ldh + n];
-          }
-      }
-    }
+    if (spread ? wave < J : wave == 0) load_resid<NCB, HH>(p, 0, M, cg, lane, hold, EveryJob{});
   }
 
   if (p.xt) {  // (fragments already in flight)
@@ -232,65 +294,17 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
       if constexpr (H2) a1[u] = *reinterpret_cast<const bf16x8*>(xs + (pos + 16 * cprp) * 16);
     }
   } else {
-    const int r0 = min(arow, M - 1), r1 = min(16 + arow, M - 1), akoff = 8 * (lane >> 4);
-#pragma unroll
-    for (int u = 0; u < KTM; ++u) {
-      const int k = min(kt0 + u, ktl) * 32 + akoff;
-      a0[u] = *reinterpret_cast<const bf16x8*>(p.x + (int64_t)r0 * p.ldx + k);
-      if constexpr (H2) a1[u] = *reinterpret_cast<const bf16x8*>(p.x + (int64_t)r1 * p.ldx + k);
-    }
+    load_x_frags_rows<KTM, H2>(p.x, p.ldx, M, kt0, ktl, lane, a0, a1);
   }
 
   // 2. MFMA over this wave's k-tiles (raw operand: the LayerNorm is applied in the epilogue)
   KW_DEC_STAMP(1);
   f32x4 c0[NCB], c1[NCB];
-#pragma unroll
-  for (int c = 0; c < NCB; ++c) {
-    c0[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-    c1[c] = c0[c];
-  }
-#pragma unroll
-  for (int u = 0; u < KTM; ++u) {
-    if (kt0 + u < kt1) {
-#pragma unroll
-      for (int c = 0; c < NCB; ++c) {
-        c0[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[u], w[c][u], c0[c], 0, 0, 0);
-        if constexpr (H2) c1[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[u], w[c][u], c1[c], 0, 0, 0);
-      }
-    }
-  }
+  mfma_tile<KTM, NCB, H2>(a0, a1, w, kt0, kt1, c0, c1);
 
-  // 3. LayerNorm statistics of the 32 rows (the workgroup's waves cover K: host-checked, ksn == 1), on
-  //    the matrix cores: X.1 gives the row sums, X.X^T's diagonal the row sums of squares (the A
-  //    fragment of X is also the B fragment of X^T); fixed-order fp32 accumulation, waves summed in
-  //    order through LDS
-  if constexpr (LNA) {
-    bf16x8 ones;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
-    f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = s0, q0 = s0, q1 = s0;
-#pragma unroll
-    for (int u = 0; u < KTM; ++u)
-      if (kt0 + u < kt1) {
-        s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[u], ones, s0, 0, 0, 0);
-        if constexpr (H2) s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[u], ones, s1, 0, 0, 0);
-        q0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[u], a0[u], q0, 0, 0, 0);
-        if constexpr (H2) q1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[u], a1[u], q1, 0, 0, 0);
-      }
-    // C layout: lane holds rows 4*(lane>>4)+i, column lane&15
-    if ((lane & 15) == 0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        rpart[wave][4 * (lane >> 4) + i][0] = s0[i];
-        if constexpr (H2) rpart[wave][16 + 4 * (lane >> 4) + i][0] = s1[i];
-      }
-    }
-    const int di = (lane & 15) - 4 * (lane >> 4);  // diagonal element of this lane, if any
-    if (di >= 0 && di < 4) {
-      rpart[wave][lane & 15][1] = q0[di];
-      if constexpr (H2) rpart[wave][16 + (lane & 15)][1] = q1[di];
-    }
-  }
+  // 3. LayerNorm statistics of the 32 rows (the workgroup's waves cover K: host-checked, ksn == 1) on the matrix
+  //    cores, waves summed in order through LDS
+  if constexpr (LNA) ln_row_partials<KTM, H2>(a0, a1, kt0, kt1, lane, rpart[wave]);
 
   // 4. reduce the waves' K slices (fixed order); wave 0 continues
   KW_DEC_STAMP(2);
@@ -308,26 +322,6 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
     __syncthreads();
     if (wave >= J) return;
     const int cj = wave / HH, hj = wave - cj * HH;
-    if constexpr (LNA) {
-      if (lane < 16) {
-        const int m = 16 * hj + lane;
-        float sx = 0.f, sq = 0.f;
-        for (int w2 = 0; w2 < nw; ++w2) {
-          sx += rpart[w2][m][0];
-          sq += rpart[w2][m][1];
-        }
-        const float inv = 1.f / (float)p.K;
-        const float mean = sx * inv;
-        rstat[m][0] = mean;
-        rstat[m][1] = rsqrtf(fmaxf(sq * inv - mean * mean, 0.f) + p.ln_eps);
-      }
-      __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-      __builtin_amdgcn_wave_barrier();
-      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    }
-    f32x4 acc = red[0][cj][hj][lane];
-    for (int w2 = 1; w2 < nw; ++w2) acc += red[w2][cj][hj][lane];
-    KW_DEC_STAMP(3);
     float bn = 0.f, cs = 0.f, hv[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int c = 0; c < NCB; ++c)
@@ -340,24 +334,8 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
 #pragma unroll
             for (int r = 0; r < 4; ++r) hv[r] = hold[c][hh][r];
       }
-    const int nb = (cg * NCB + cj) * 16;  // the job's first column
-    const int n = nb + (lane & 15);
-    float v4[4];
-#pragma unroll
-    for (int r = 0; r < 4; ++r) {
-      const int m = 16 * hj + 4 * (lane >> 4) + r;
-      float v = acc[r];
-      if constexpr (LNA) v = rstat[m][1] * (v - rstat[m][0] * cs);
-      v += bn;
-      if constexpr (EPI == KW_EPI_RESID) {
-        v += hv[r];
-      } else {
-        if (p.gelu) v = sizeof(TC) == 2 ? gelu_bf16out(v) : gelu_erf(v);
-        if (n < p.scale_cols) v *= p.scale;
-      }
-      v4[r] = v;
-    }
-    store_block16<EPI, TC, true>(p, stg[wave], v4, 16 * hj, M, nb, lane);
+    tile_job_epilogue<NCB, LNA, EPI, TC, true>(p, red, rpart, rstat, stg[wave], nw, cj, hj, bn, cs, hv, 0, M,
+                                               (cg * NCB + cj) * 16, lane, [&] { KW_DEC_STAMP(3); });
     KW_DEC_STAMP(4);
     KW_DEC_STAMP_FLUSH
     return;
@@ -378,17 +356,7 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
       }
   }
   if constexpr (LNA) {  // wave 0: lane r < 32 sums row r's wave partials in wave order -> (mean, rstd)
-    if (lane < 32) {
-      float sx = 0.f, sq = 0.f;
-      for (int w2 = 0; w2 < nw; ++w2) {
-        sx += rpart[w2][lane][0];
-        sq += rpart[w2][lane][1];
-      }
-      const float inv = 1.f / (float)p.K;
-      const float mean = sx * inv;
-      rstat[lane][0] = mean;
-      rstat[lane][1] = rsqrtf(fmaxf(sq * inv - mean * mean, 0.f) + p.ln_eps);
-    }
+    if (lane < 32) ln_finish_row(rpart, nw, lane, p.K, p.ln_eps, rstat);
   }
 
   // 5. K-split seam: publish the partial tile write-through, count arrivals, the last one sums in order.  r06: each
@@ -450,16 +418,8 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
 #pragma unroll
       for (int r = 0; r < 4; ++r) {
         const int m = 16 * hh + 4 * (lane >> 4) + r;
-        float v = hh ? c1[c][r] : c0[c][r];
-        if constexpr (LNA) v = rstat[m][1] * (v - rstat[m][0] * cs);  // LN(x) W'^T
-        v += bn;
-        if constexpr (EPI == KW_EPI_RESID) {
-          v += hold[c][hh][r];
-        } else {
-          if (p.gelu) v = sizeof(TC) == 2 ? gelu_bf16out(v) : gelu_erf(v);
-          if (n < p.scale_cols) v *= p.scale;
-        }
-        vals[c][hh][r] = v;
+        vals[c][hh][r] = epi_value<LNA, EPI, TC>(p, hh ? c1[c][r] : c0[c][r], rstat[m], n, cs, bn,
+                                                  EPI == KW_EPI_RESID ? hold[c][hh][r] : 0.f);
       }
     }
   }
@@ -475,9 +435,7 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
       for (int hh = 0; hh < (H2 ? 2 : 1); ++hh)
 #pragma unroll
         for (int r = 0; r < 4; ++r) stg[(16 * hh + 4 * (lane >> 4) + r) * SW + c * 16 + (lane & 15)] = vals[c][hh][r];
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-    __builtin_amdgcn_wave_barrier();
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    wave_lds_sync();
     const int n0 = cg * NCB * 16;
     constexpr bool F32 = EPI == KW_EPI_RESID || sizeof(TC) == 4, BF16 = EPI == KW_EPI_RESID || sizeof(TC) == 2;
     if constexpr (F32) {
@@ -506,23 +464,9 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
     }
   } else {
 #pragma unroll
-    for (int c = 0; c < NCB; ++c) {
-      const int n = (cg * NCB + c) * 16 + (lane & 15);
+    for (int c = 0; c < NCB; ++c)
 #pragma unroll
-      for (int hh = 0; hh < (H2 ? 2 : 1); ++hh)
-#pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = 16 * hh + 4 * (lane >> 4) + r;
-          if (n >= p.N || m >= M) continue;
-          const float v = vals[c][hh][r];
-          if constexpr (EPI == KW_EPI_RESID) {
-            p.h[(int64_t)m * p.ldh + n] = v;
-            *hb_at(p, m, n) = f2bf(v);
-          } else {
-            TypeIO<TC>::st(reinterpret_cast<TC*>(p.C) + (int64_t)m * p.ldc + n, v);
-          }
-        }
-    }
+      for (int hh = 0; hh < HH; ++hh) store_elems<EPI, TC, true>(p, vals[c][hh], 16 * hh, M, (cg * NCB + c) * 16, lane);
   }
   KW_DEC_STAMP(4);
   KW_DEC_STAMP_FLUSH
@@ -532,20 +476,10 @@ template <int KTM, int NCB, bool LNA, int EPI, typename TC, bool H2 = true>
 __global__ __launch_bounds__(512) void dec_linear_kernel(DecP p0, int ksn) {
   // blockIdx.z = 32-row chunk: a launch covers M rows as independent 32-row tiles (their workgroups
   // run concurrently and the repeat weight reads of the later chunks hit the caches)
-  DecP p = p0;
+  DecP p = rows_window(p0, p0.zrows * blockIdx.z, p0.zrows, sizeof(TC));  // (fragment-major: 16-row chunks only)
   if (ksn > 1) {  // K-split seam: each chunk has its own counters and partial slabs
     p.cnt += blockIdx.z * gridDim.x;
     p.slab += (int64_t)blockIdx.z * gridDim.x * ksn * (NCB * 512);
-  }
-  if (blockIdx.z) {
-    const int m0 = p0.zrows * blockIdx.z;
-    p.M = min(p0.zrows, p0.M - m0);
-    p.x += p0.xt ? m0 * 32 : m0 * p0.ldx;  // (fragment-major: 16-row chunks only -- the next row tile, 512 elements on)
-    if (p.C) p.C = reinterpret_cast<char*>(p.C) + (int64_t)m0 * p0.ldc * (sizeof(TC));
-    if (p.h) p.h += m0 * p0.ldh;
-    if (p.hb) p.hb += p0.hbt ? m0 * 32 : m0 * p0.ldh;  // (fragment-major: the next row tile, as x)
-  } else {
-    p.M = min(p0.zrows, p0.M);
   }
   dec_linear_body<KTM, NCB, LNA, EPI, TC, H2>(p, ksn, blockIdx.x, blockIdx.y, blockDim.x >> 6);
 }
@@ -554,8 +488,8 @@ __global__ __launch_bounds__(512) void dec_linear_kernel(DecP p0, int ksn) {
 // columns' weight fragments in registers and walks ``zper`` 32-row chunks.  (One z-slice per chunk
 // re-streams the weights per chunk and runs as many rounds of workgroups as there are chunks, each a
 // full load round trip: 50 us for fc1 at 320 rows.)  Per chunk the arithmetic is dec_linear_kernel's
-// operation for operation -- the same fragments, MFMA order, wave-ordered reduction and epilogue --
-// so results are bitwise those of the chunked launch.
+// operation for operation -- the same fragments, MFMA order, wave-ordered reduction and epilogue, through the
+// same helpers -- so results are bitwise those of the chunked launch.
 template <int KTM, int NCB, bool LNA, int EPI, typename TC>
 __global__ __launch_bounds__(512) void dec_linear_rows_kernel(DecP p, int zper) {
   __shared__ f32x4 red[MAXW][NCB][2][64];
@@ -567,15 +501,10 @@ __global__ __launch_bounds__(512) void dec_linear_rows_kernel(DecP p, int zper) 
   const int nkt = p.K >> 5;
   const int kt0 = (nkt * wave) / nw, kt1 = (nkt * (wave + 1)) / nw;  // <= KTM (host-checked)
   const int ktl = max(kt1 - 1, kt0);
-  const int arow = lane & 15, akoff = 8 * (lane >> 4);
   const int nz = (p.M + 31) / 32;
   const int z0 = blockIdx.z * zper, z1 = min(nz, z0 + zper);
   bf16x8 w[NCB][KTM];
-#pragma unroll
-  for (int c = 0; c < NCB; ++c)
-#pragma unroll
-    for (int u = 0; u < KTM; ++u)
-      w[c][u] = __builtin_nontemporal_load(p.W + ((int64_t)(cg * NCB + c) * nkt + min(kt0 + u, ktl)) * 64 + lane);
+  load_w_frags<KTM, NCB, true>(p.W, cg, nkt, kt0, ktl, lane, w);
   float ebias[NCB], ecsum[NCB];
 #pragma unroll
   for (int c = 0; c < NCB; ++c) {
@@ -585,90 +514,18 @@ __global__ __launch_bounds__(512) void dec_linear_rows_kernel(DecP p, int zper) 
   }
   for (int z = z0; z < z1; ++z) {
     const int m0 = 32 * z, M = min(32, p.M - m0);
-    const bf16_t* x = p.x + (int64_t)m0 * p.ldx;
     bf16x8 a0[KTM], a1[KTM];
-    {
-      const int r0 = min(arow, M - 1), r1 = min(16 + arow, M - 1);
-#pragma unroll
-      for (int u = 0; u < KTM; ++u) {
-        const int k = min(kt0 + u, ktl) * 32 + akoff;
-        a0[u] = *reinterpret_cast<const bf16x8*>(x + (int64_t)r0 * p.ldx + k);
-        a1[u] = *reinterpret_cast<const bf16x8*>(x + (int64_t)r1 * p.ldx + k);
-      }
-    }
+    load_x_frags_rows<KTM, true>(p.x + (int64_t)m0 * p.ldx, p.ldx, M, kt0, ktl, lane, a0, a1);
     // the residual values, loaded by the wave that writes them in the epilogue (NCB == 2: its job (c, hh))
     float hold[NCB][2][4];
     if constexpr (EPI == KW_EPI_RESID && NCB == 2) {
-#pragma unroll
-      for (int c = 0; c < NCB; ++c) {
-        const int n = min((cg * NCB + c) * 16 + (lane & 15), p.N - 1);
-#pragma unroll
-        for (int hh = 0; hh < 2; ++hh)
-          if ((2 * c + hh) % nw == wave) {
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int m = min(16 * hh + 4 * (lane >> 4) + r, M - 1);
-              hold[c][hh][r] = p.h[(int64_t)(m0 + m) * p.ldh + n];
-            }
-          }
-      }
+      load_resid<NCB, 2>(p, m0, M, cg, lane, hold, [&](int c, int hh) { return (2 * c + hh) % nw == wave; });
     } else if constexpr (EPI == KW_EPI_RESID) {
-      if (wave == 0) {
-#pragma unroll
-        for (int c = 0; c < NCB; ++c) {
-          const int n = min((cg * NCB + c) * 16 + (lane & 15), p.N - 1);
-#pragma unroll
-          for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-            for (int r = 0; r < 4; ++r) {
-              const int m = min(16 * hh + 4 * (lane >> 4) + r, M - 1);
-              hold[c][hh][r] = p.h[(int64_t)(m0 + m) * p.ldh + n];
-            }
-        }
-      }
+      if (wave == 0) load_resid<NCB, 2>(p, m0, M, cg, lane, hold, EveryJob{});
     }
     f32x4 c0[NCB], c1[NCB];
-#pragma unroll
-    for (int c = 0; c < NCB; ++c) {
-      c0[c] = f32x4{0.f, 0.f, 0.f, 0.f};
-      c1[c] = c0[c];
-    }
-#pragma unroll
-    for (int u = 0; u < KTM; ++u) {
-      if (kt0 + u < kt1) {
-#pragma unroll
-        for (int c = 0; c < NCB; ++c) {
-          c0[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[u], w[c][u], c0[c], 0, 0, 0);
-          c1[c] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[u], w[c][u], c1[c], 0, 0, 0);
-        }
-      }
-    }
-    if constexpr (LNA) {  // row statistics on the matrix cores, as dec_linear_kernel step 3
-      bf16x8 ones;
-#pragma unroll
-      for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
-      f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = s0, q0 = s0, q1 = s0;
-#pragma unroll
-      for (int u = 0; u < KTM; ++u)
-        if (kt0 + u < kt1) {
-          s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[u], ones, s0, 0, 0, 0);
-          s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[u], ones, s1, 0, 0, 0);
-          q0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[u], a0[u], q0, 0, 0, 0);
-          q1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[u], a1[u], q1, 0, 0, 0);
-        }
-      if ((lane & 15) == 0) {
-#pragma unroll
-        for (int i = 0; i < 4; ++i) {
-          rpart[wave][4 * (lane >> 4) + i][0] = s0[i];
-          rpart[wave][16 + 4 * (lane >> 4) + i][0] = s1[i];
-        }
-      }
-      const int di = (lane & 15) - 4 * (lane >> 4);
-      if (di >= 0 && di < 4) {
-        rpart[wave][lane & 15][1] = q0[di];
-        rpart[wave][16 + (lane & 15)][1] = q1[di];
-      }
-    }
+    mfma_tile<KTM, NCB, true>(a0, a1, w, kt0, kt1, c0, c1);
+    if constexpr (LNA) ln_row_partials<KTM, true>(a0, a1, kt0, kt1, lane, rpart[wave]);
     if (NCB == 2 || nw > 1) {
 #pragma unroll
       for (int c = 0; c < NCB; ++c) {
@@ -679,50 +536,21 @@ __global__ __launch_bounds__(512) void dec_linear_rows_kernel(DecP p, int zper) 
     __syncthreads();
     if constexpr (NCB == 2) {
       // two column blocks: the epilogue's four jobs -- (column block c, row half hh) -- spread over the waves (job
-      // = wave + i nw), each summing its partial tiles over the waves in wave order as wave 0 alone does below and
-      // forming its row half's LayerNorm statistics itself (LDS is in order within a wave; two jobs of one half
-      // write the same values): bitwise the same results.  fc1 at 320 rows 41.4 -> 36.5 us; one column block keeps
-      // wave 0 alone, which measured faster there (profiles/r05al_rows_epilogue_ab.txt)
+      // = wave + i nw), each as tile_job_epilogue: bitwise wave 0 alone doing all four.  fc1 at 320 rows 41.4 ->
+      // 36.5 us; one column block keeps wave 0 alone, which measured faster there
+      // (profiles/r05al_rows_epilogue_ab.txt)
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         const int job = wave + i * nw;
         if (job >= 4) break;
         const int c = job >> 1, hh = job & 1;
-        if constexpr (LNA) {
-          if (lane < 16) {
-            const int m = 16 * hh + lane;
-            float sx = 0.f, sq = 0.f;
-            for (int w2 = 0; w2 < nw; ++w2) {
-              sx += rpart[w2][m][0];
-              sq += rpart[w2][m][1];
-            }
-            const float inv = 1.f / (float)p.K;
-            const float mean = sx * inv;
-            rstat[m][0] = mean;
-            rstat[m][1] = rsqrtf(fmaxf(sq * inv - mean * mean, 0.f) + p.ln_eps);
-          }
-        }
-        f32x4 acc = red[0][c][hh][lane];
-        for (int w2 = 1; w2 < nw; ++w2) acc += red[w2][c][hh][lane];
-        const int n = (cg * NCB + c) * 16 + (lane & 15);
-        const float bn = ebias[c];
-        const float cs = ecsum[c];
-        float v4[4];
+        float hv[4] = {0.f, 0.f, 0.f, 0.f};
+        if constexpr (EPI == KW_EPI_RESID) {
 #pragma unroll
-        for (int r = 0; r < 4; ++r) {
-          const int m = 16 * hh + 4 * (lane >> 4) + r;
-          float v = acc[r];
-          if constexpr (LNA) v = rstat[m][1] * (v - rstat[m][0] * cs);
-          v += bn;
-          if constexpr (EPI == KW_EPI_RESID) {
-            v += hold[c][hh][r];
-          } else {
-            if (p.gelu) v = sizeof(TC) == 2 ? gelu_bf16out(v) : gelu_erf(v);
-            if (n < p.scale_cols) v *= p.scale;
-          }
-          v4[r] = v;
+          for (int r = 0; r < 4; ++r) hv[r] = hold[c][hh][r];
         }
-        store_block16<EPI, TC>(p, stg[wave], v4, m0 + 16 * hh, m0 + M, (cg * NCB + c) * 16, lane);
+        tile_job_epilogue<NCB, LNA, EPI, TC, false>(p, red, rpart, rstat, stg[wave], nw, c, hh, ebias[c], ecsum[c], hv, m0, M,
+                                                    (cg * NCB + c) * 16, lane, [] {});
       }
     } else if (wave == 0) {
       for (int w2 = 1; w2 < nw; ++w2)
@@ -732,39 +560,19 @@ __global__ __launch_bounds__(512) void dec_linear_rows_kernel(DecP p, int zper) 
           c1[c] += red[w2][c][1][lane];
         }
       if constexpr (LNA) {
-        if (lane < 32) {
-          float sx = 0.f, sq = 0.f;
-          for (int w2 = 0; w2 < nw; ++w2) {
-            sx += rpart[w2][lane][0];
-            sq += rpart[w2][lane][1];
-          }
-          const float inv = 1.f / (float)p.K;
-          const float mean = sx * inv;
-          rstat[lane][0] = mean;
-          rstat[lane][1] = rsqrtf(fmaxf(sq * inv - mean * mean, 0.f) + p.ln_eps);
-        }
+        if (lane < 32) ln_finish_row(rpart, nw, lane, p.K, p.ln_eps, rstat);
       }
 #pragma unroll
       for (int c = 0; c < NCB; ++c) {
         const int n = (cg * NCB + c) * 16 + (lane & 15);
-        const float bn = ebias[c];
-        const float cs = ecsum[c];
 #pragma unroll
         for (int hh = 0; hh < 2; ++hh) {
           float v4[4];
 #pragma unroll
           for (int r = 0; r < 4; ++r) {
             const int m = 16 * hh + 4 * (lane >> 4) + r;
-            float v = hh ? c1[c][r] : c0[c][r];
-            if constexpr (LNA) v = rstat[m][1] * (v - rstat[m][0] * cs);
-            v += bn;
-            if constexpr (EPI == KW_EPI_RESID) {
-              v += hold[c][hh][r];
-            } else {
-              if (p.gelu) v = sizeof(TC) == 2 ? gelu_bf16out(v) : gelu_erf(v);
-              if (n < p.scale_cols) v *= p.scale;
-            }
-            v4[r] = v;
+            v4[r] = epi_value<LNA, EPI, TC>(p, hh ? c1[c][r] : c0[c][r], rstat[m], n, ecsum[c], ebias[c],
+                                            EPI == KW_EPI_RESID ? hold[c][hh][r] : 0.f);
           }
           store_block16<EPI, TC>(p, stg[0], v4, m0 + 16 * hh, m0 + M, (cg * NCB + c) * 16, lane);
         }
@@ -790,11 +598,6 @@ __device__ __forceinline__ bf16x8 lmr_lds_read(const char* p) {
   bf16x8 v;
   asm volatile("ds_read_b128 %0, %1" : "=v"(v) : "v"(lds_u32(p)) : "memory");
   return v;
-}
-__device__ __forceinline__ void lmr_barrier() {  // raw s_barrier: no implicit vmcnt(0) drain
-  asm volatile("" ::: "memory");
-  __builtin_amdgcn_s_barrier();
-  asm volatile("" ::: "memory");
 }
 
 // NWV waves (16 columns each); G 16-B LDS-DMA pieces per lane per slice (a slice holds 16 NWV G rows); NZ 32-row
@@ -855,7 +658,7 @@ __global__ __launch_bounds__(64 * NWV) void lm_head_rows_kernel(DecP p) {
     for (int u = 0; u < PD; ++u) {
       const int kt = kb + u;
       asm volatile("s_waitcnt vmcnt(%0)" ::"n"(YOUNGER) : "memory");
-      lmr_barrier();
+      raw_barrier();  // (no implicit vmcnt(0) drain)
       stage((kt + LEAD) % NBUF, min(kt + LEAD, nkt - 1));
       const char* a = abuf[kt % NBUF];
       bf16x8 fa[2][2];
@@ -922,9 +725,9 @@ __global__ __launch_bounds__(64 * NWV) void lm_head_rows_kernel(DecP p) {
         const int m = 32 * z + 16 * hh + 4 * fc + r;
         if (z < nz && m < M) {
           const float mean = rsum[m] * inv;
-          const float rstd = rsqrtf(fmaxf(rsq[m] * inv - mean * mean, 0.f) + p.ln_eps);
+          const float rstd = ln_rstd(rsq[m], inv, mean, p.ln_eps);
           const float v = hh ? acc1[z][r] : acc0[z][r];
-          reinterpret_cast<float*>(p.C)[(int64_t)m * p.ldc + n] = rstd * (v - mean * cs) + bn;
+          reinterpret_cast<float*>(p.C)[(int64_t)m * p.ldc + n] = ln_fold(v, mean, rstd, cs) + bn;
         }
       }
   }
@@ -946,6 +749,8 @@ constexpr int LMH_MAXG = 8;  // column groups per workgroup (epilogue constants 
 constexpr int LMH_ECJ = 4;   // epilogue-constant columns staged per thread (host-checked: 64 * waves * 4 >= 32 * groups)
 constexpr int LMH_MAX_ROWS = 32;  // rows up to which the LM head takes lm_head_kernel (weight groups: three in
                                   // registers, two in flight beside the one being multiplied)
+constexpr int LMG_HIST = 7;  // greedy tail: id-history loads per lane of the EOS scan -- it sees LMG_HIST * 64 positions
+                             // after begin_index, so kw_dec_lm_greedy takes max_length - begin_index up to that
 
 __device__ __forceinline__ void lmh_barrier() {  // LDS writes visible, then s_barrier: global loads stay in flight
   asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory");
@@ -1064,10 +869,7 @@ __device__ __forceinline__ void lm_greedy_tail(const LmGreedy& sg, const float (
 
 template <bool AM>
 __global__ __launch_bounds__(512) void lm_head_kernel(DecP p0, int groups_per_wg, LmGreedy sg) {
-  DecP p = p0;  // blockIdx.z = 32-row chunk (beam rows), as in dec_linear_kernel
-  p.M = min(32, p0.M - 32 * (int)blockIdx.z);
-  p.x += (int64_t)32 * blockIdx.z * p0.ldx;
-  if (p0.C) p.C = reinterpret_cast<float*>(p0.C) + (int64_t)32 * blockIdx.z * p0.ldc;
+  const DecP p = rows_window(p0, 32 * (int)blockIdx.z, 32, sizeof(float));  // blockIdx.z = 32-row chunk (beam rows)
   __shared__ f32x4 red[3][MAXW][LMH_NCB][2][64];  // per-wave partial tiles, one slot per group in flight
   __shared__ float rpart[MAXW][32][2];
   __shared__ float rstat[32][2];
@@ -1080,7 +882,7 @@ __global__ __launch_bounds__(512) void lm_head_kernel(DecP p0, int groups_per_wg
   const int kt0 = (nkt * wave) / nw, kt1 = (nkt * (wave + 1)) / nw;  // <= LMH_KTM (host-checked)
   const int ktl = max(kt1 - 1, kt0);
   const int M = p.M;
-  const int n_groups = (p.N + 16 * LMH_NCB - 1) / (16 * LMH_NCB);
+  const int n_groups = col_groups(p.N, LMH_NCB);
   const int g0 = blockIdx.x * groups_per_wg, g1 = min(n_groups, g0 + groups_per_wg);
   if (g0 >= g1) return;
   // the run's weights through a bounds-checked buffer resource: a prefetch past the run (g >= g1) returns zeros
@@ -1117,35 +919,21 @@ __global__ __launch_bounds__(512) void lm_head_kernel(DecP p0, int groups_per_wg
   // AM: workgroup r < M scans row r's id history for EOS (stopping_criteria.py:75-77) while the weights stream --
   // wave 0, positions begin + lane + 64 u, loads clamped into the row (no wait on cur_len before issuing them)
   [[maybe_unused]] int row_fin = 0;
-  [[maybe_unused]] int64_t hist[AM ? 7 : 1];
+  [[maybe_unused]] int64_t hist[AM ? LMG_HIST : 1];
   if constexpr (AM) {
     step_len = *sg.cur_len;
     if ((int)blockIdx.x < M && wave == 0) {
       const int64_t* ids = sg.ids + (int64_t)blockIdx.x * sg.ids_stride;
 #pragma unroll
-      for (int u = 0; u < 7; ++u) hist[u] = ids[min(sg.begin_index + lane + 64 * u, (int)sg.ids_stride - 1)];
+      for (int u = 0; u < LMG_HIST; ++u) hist[u] = ids[min(sg.begin_index + lane + 64 * u, (int)sg.ids_stride - 1)];
     }
   }
   // activation fragments of this wave's k-range, once (rows lane&15 and 16 + lane&15)
   bf16x8 a0[LMH_KTM], a1[LMH_KTM];
-  if (p.xt) {  // fragment-major x (M <= 32, one z-chunk): each fragment one contiguous 1-KB piece, as dec_linear_body
-    const bf16x8* xf = reinterpret_cast<const bf16x8*>(p.x) + lane;
-    const int t1 = p.xt > 1 ? 64 : 0;
-#pragma unroll
-    for (int u = 0; u < LMH_KTM; ++u) {
-      const bf16x8* f = xf + (int64_t)(min(kt0 + u, ktl) * p.xt) * 64;
-      a0[u] = *f;
-      a1[u] = f[t1];
-    }
-  } else {
-    const int r0 = min(lane & 15, M - 1), r1 = min(16 + (lane & 15), M - 1), akoff = 8 * (lane >> 4);
-#pragma unroll
-    for (int u = 0; u < LMH_KTM; ++u) {
-      const int k = min(kt0 + u, ktl) * 32 + akoff;
-      a0[u] = *reinterpret_cast<const bf16x8*>(p.x + (int64_t)r0 * p.ldx + k);
-      a1[u] = *reinterpret_cast<const bf16x8*>(p.x + (int64_t)r1 * p.ldx + k);
-    }
-  }
+  if (p.xt)  // fragment-major x (M <= 32, one z-chunk)
+    load_x_frags_tiled<LMH_KTM, true>(p.x, p.xt, kt0, ktl, lane, a0, a1);
+  else
+    load_x_frags_rows<LMH_KTM, true>(p.x, p.ldx, M, kt0, ktl, lane, a0, a1);
   bf16x8 wa[LMH_NCB][LMH_KTM], wb[LMH_NCB][LMH_KTM], wc[LMH_NCB][LMH_KTM];
   wload(g0, wa);
   wload(g0 + 1, wb);
@@ -1169,45 +957,10 @@ __global__ __launch_bounds__(512) void lm_head_kernel(DecP p0, int groups_per_wg
     za1[u] = in ? a1[u] : bf16x8{};
   }
   // LayerNorm statistics of the 32 rows on the matrix cores (as dec_linear_kernel step 3)
-  {
-    bf16x8 ones;
-#pragma unroll
-    for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
-    f32x4 s0 = f32x4{0.f, 0.f, 0.f, 0.f}, s1 = s0, q0 = s0, q1 = s0;
-#pragma unroll
-    for (int u = 0; u < LMH_KTM; ++u)
-      if (kt0 + u < kt1) {
-        s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[u], ones, s0, 0, 0, 0);
-        s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[u], ones, s1, 0, 0, 0);
-        q0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[u], a0[u], q0, 0, 0, 0);
-        q1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[u], a1[u], q1, 0, 0, 0);
-      }
-    if ((lane & 15) == 0) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        rpart[wave][4 * (lane >> 4) + i][0] = s0[i];
-        rpart[wave][16 + 4 * (lane >> 4) + i][0] = s1[i];
-      }
-    }
-    const int di = (lane & 15) - 4 * (lane >> 4);
-    if (di >= 0 && di < 4) {
-      rpart[wave][lane & 15][1] = q0[di];
-      rpart[wave][16 + (lane & 15)][1] = q1[di];
-    }
-    __syncthreads();  // (also the epilogue constants: loaded before it)
-    if (tid < 32) {
-      float sx = 0.f, sq = 0.f;
-      for (int w2 = 0; w2 < nw; ++w2) {
-        sx += rpart[w2][tid][0];
-        sq += rpart[w2][tid][1];
-      }
-      const float inv = 1.f / (float)p.K;
-      const float mean = sx * inv;
-      rstat[tid][0] = mean;
-      rstat[tid][1] = rsqrtf(fmaxf(sq * inv - mean * mean, 0.f) + p.ln_eps);
-    }
-    __syncthreads();
-  }
+  ln_row_partials<LMH_KTM, true>(a0, a1, kt0, kt1, lane, rpart[wave]);
+  __syncthreads();  // (also the epilogue constants: loaded before it)
+  if (tid < 32) ln_finish_row(rpart, nw, tid, p.K, p.ln_eps, rstat);
+  __syncthreads();
   // walk the run: groups g+1 and g+2 in flight while group g is multiplied, reduced and stored
   auto body = [&](int g, int slot, bf16x8 (&w)[LMH_NCB][LMH_KTM]) {
     f32x4 c0[LMH_NCB], c1[LMH_NCB];
@@ -1237,7 +990,7 @@ __global__ __launch_bounds__(512) void lm_head_kernel(DecP p0, int groups_per_wg
         for (int r = 0; r < 4; ++r) {
           const int m = 16 * hh + 4 * (lane >> 4) + r;
           if (m < M) {
-            obuf[m][(g - g0) * LMH_NCB * 16 + c * 16 + (lane & 15)] = rstat[m][1] * (acc[r] - rstat[m][0] * cs) + bn;
+            obuf[m][(g - g0) * LMH_NCB * 16 + c * 16 + (lane & 15)] = ln_fold(acc[r], rstat[m][0], rstat[m][1], cs) + bn;
           }
         }
       }
@@ -1269,7 +1022,7 @@ __global__ __launch_bounds__(512) void lm_head_kernel(DecP p0, int groups_per_wg
     if ((int)blockIdx.x < M && wave == 0) {
       int f = 0;
 #pragma unroll
-      for (int u = 0; u < 7; ++u) f |= (sg.begin_index + lane + 64 * u < step_len && hist[u] == sg.eos_id) ? 1 : 0;
+      for (int u = 0; u < LMG_HIST; ++u) f |=(sg.begin_index + lane + 64 * u < step_len && hist[u] == sg.eos_id) ? 1 : 0;
       row_fin = __builtin_amdgcn_ballot_w64(f != 0) != 0;
     }
     lm_greedy_tail(sg, obuf, smask, ncol, g0 * LMH_NCB * 16, M, step_len, row_fin);
@@ -1333,7 +1086,7 @@ Geo choose(int64_t N, int64_t K) {
 // workgroup per CU) and for the split-K workgroups (fc2: each stages its 32 rows x 864-element slice, 55 KB,
 // two workgroups per CU: 10.3 vs 10.7 us, bitwise equal, profiles/r03_lab_notes.md r03y); the LM head's
 // 1,621-workgroup grid keeps direct fragment loads at four workgroups per CU.
-bool use_xlds(int64_t N, const Geo& g) { return g.ks > 1 || (N + 16 * g.ncb - 1) / (16 * g.ncb) <= 256; }
+bool use_xlds(int64_t N, const Geo& g) { return g.ks > 1 || col_groups(N, g.ncb) <= 256; }
 size_t x_lds_bytes_for(int nkt, int ks, bool xlds) { return xlds ? x_lds_bytes((nkt + ks - 1) / ks) : 0; }
 // the image of a <= 16-row chunk (row split): only its rows' pieces are staged
 size_t x_lds_bytes_rows(int tiles, int rows, bool xlds) {
@@ -1360,9 +1113,9 @@ hipError_t launch_grid(const DecP& q, dim3 grid, dim3 block, size_t shm, int ks,
 
 template <int KTM, int NCB, bool LNA, int EPI, typename TC>
 hipError_t launch_one(const DecP& p, const Geo& g, hipStream_t s) {
-  const int nkt = p.K / 32;
+  const int nkt = p.K / 32, ncg = col_groups(p.N, NCB);
   if (g.ks == 1 && p.M > 32) {  // many rows: weight-stationary workgroups over row chunks
-    const int ncg = (p.N + 16 * NCB - 1) / (16 * NCB), nz = (p.M + 31) / 32;
+    const int nz = (p.M + 31) / 32;
     const int zg0 = std::max(1, std::min(nz, (2 * device_cus()) / ncg));
     const int zper = (nz + zg0 - 1) / zg0, zg = (nz + zper - 1) / zper;
     hipLaunchKernelGGL((dec_linear_rows_kernel<KTM, NCB, LNA, EPI, TC>), dim3((unsigned)ncg, 1, (unsigned)zg),
@@ -1374,7 +1127,6 @@ hipError_t launch_one(const DecP& p, const Geo& g, hipStream_t s) {
   // half (the H2 = false instantiation), every output element by the same operations (rows are independent):
   // bitwise the 32-row launch.  o 5.05 -> 4.13-4.29 us; fc1 (160 -> 320 workgroups, two per CU) measured
   // 8.6 -> 8.7-8.9 us, so it keeps one launch of 32-row tiles (profiles/r04o_rowsplit_ab.txt)
-  const int ncg = (p.N + 16 * NCB - 1) / (16 * NCB);
   const bool split = g.ks == 1 && p.M > 16 && p.M <= 32 && 2 * ncg <= device_cus();
   DecP q = p;
   q.zrows = split ? 16 : 32;
@@ -1397,25 +1149,24 @@ hipError_t launch(const DecP& p, bool resid, const Geo& g, bool c_f32, hipStream
   return g.ncb == 2 ? launch_k<10, 2>(p, resid, g, c_f32, s) : launch_k<10, 1>(p, resid, g, c_f32, s);
 }
 
-// the LM head's column groups per workgroup: one run per CU
-int lmh_groups_per_wg(int64_t N) {
-  const int ncu = device_cus();
-  const int groups = (int)((N + 16 * LMH_NCB - 1) / (16 * LMH_NCB));
-  return (groups + ncu - 1) / ncu;
+// The persistent LM head's launch (lm_head_kernel, with or without the greedy tail): N columns in groups of LMH_NCB
+// column blocks, one contiguous run of per_wg groups per workgroup -- one run per CU -- on waves of LMH_KTM k-tiles
+struct LmhGeo {
+  int groups, per_wg, grid, waves;
+};
+LmhGeo lmh_geo(int64_t N, int nkt) {
+  LmhGeo g;
+  g.groups = (int)col_groups(N, LMH_NCB);
+  g.per_wg = (g.groups + device_cus() - 1) / device_cus();
+  g.grid = (g.groups + g.per_wg - 1) / g.per_wg;
+  g.waves = (nkt + LMH_KTM - 1) / LMH_KTM;
+  return g;
 }
 
-// the persistent LM head (lm_head_kernel) covers the shape: <= 8 waves of LMH_KTM k-tiles, <= LMH_MAXG groups per
-// workgroup, the run's epilogue constants staged by one pass of LMH_ECJ per thread
-bool lmh_fits(int64_t M, int64_t N, int nkt) {
-  const int per = lmh_groups_per_wg(N);
-  return (nkt + LMH_KTM - 1) / LMH_KTM <= MAXW && M <= LMH_MAX_ROWS && per <= LMH_MAXG &&
-         64 * ((nkt + LMH_KTM - 1) / LMH_KTM) * LMH_ECJ >= per * LMH_NCB * 16;
-}
-
-// kw_dec_lm_greedy's grid (one run of column groups per workgroup, as kw_dec_linear's LM head)
-int lmg_grid(int64_t N) {
-  const int groups = (int)((N + 16 * LMH_NCB - 1) / (16 * LMH_NCB)), per = lmh_groups_per_wg(N);
-  return (groups + per - 1) / per;
+// lm_head_kernel covers the shape: <= 8 waves, <= LMH_MAXG groups per workgroup, the run's epilogue constants staged by
+// one pass of LMH_ECJ per thread
+bool lmh_fits(int64_t M, const LmhGeo& g) {
+  return g.waves <= MAXW && M <= LMH_MAX_ROWS && g.per_wg <= LMH_MAXG && 64 * g.waves * LMH_ECJ >= g.per_wg * LMH_NCB * 16;
 }
 constexpr int LMG_MAXG = 256;  // workgroups whose partials the last arriver merges (16 per lane)
 
@@ -1450,15 +1201,17 @@ DecP decp_from_args(const kw_dec_linear_args* a) {
 }  // namespace
 
 extern "C" size_t kw_dec_lm_greedy_workspace(int64_t B, int64_t V) {
-  const int64_t groups = (V + 16 * LMH_NCB - 1) / (16 * LMH_NCB);  // >= the grid on any device
+  const int64_t groups = col_groups(V, LMH_NCB);  // LmhGeo::groups: >= the grid on any device
   return 256 + (size_t)B * (size_t)std::min<int64_t>(groups, LMG_MAXG) * sizeof(unsigned long long);
 }
 
 extern "C" int kw_dec_lm_greedy_supported(int64_t B, int64_t V, int64_t d) {
-  return B >= 1 && B <= LMH_MAX_ROWS && V >= 8192 && d > 0 && d % 32 == 0 && lmh_fits(B, V, (int)(d / 32)) &&
-                 lmg_grid(V) <= LMG_MAXG
-             ? 1
-             : 0;
+  if (B < 1 || B > LMH_MAX_ROWS || V < 8192 || d <= 0 || d % 32 != 0) return 0;
+  const LmhGeo g = lmh_geo(V, (int)(d / 32));
+  // grid >= B: row r's finished flag is published by workgroup blockIdx.x == r (lm_greedy_tail).  Every shape the other
+  // conditions accept has it (V >= 8192 is 256 groups, per_wg <= LMH_MAXG = 8 leaves >= 32 workgroups): no answer
+  // changes, but a geometry change that broke it would have the merge read stale flags
+  return lmh_fits(B, g) && g.grid <= LMG_MAXG && g.grid >= B ? 1 : 0;
 }
 
 extern "C" int kw_dec_lm_greedy(const kw_dec_linear_args* a, const kw_sampler_args* g, kw_stream_t stream) {
@@ -1473,6 +1226,8 @@ extern "C" int kw_dec_lm_greedy(const kw_dec_linear_args* a, const kw_sampler_ar
     return kw_set_error_msg(KW_EUNSUPPORTED, "kw_dec_lm_greedy: no timestamps, no scores_out (use kw_greedy_step)");
   if (!kw_dec_lm_greedy_supported(a->M, a->N, a->K))
     return kw_set_error_msg(KW_EUNSUPPORTED, "kw_dec_lm_greedy: shape not covered (kw_dec_lm_greedy_supported)");
+  if (g->max_length - g->begin_index > LMG_HIST * 64)  // (the EOS scan would miss a later position's history)
+    return kw_set_error_msg(KW_EUNSUPPORTED, "kw_dec_lm_greedy: max_length - begin_index beyond the 448 positions the EOS scan covers");
   if (g->ws_bytes < kw_dec_lm_greedy_workspace(a->M, a->N) || (uintptr_t)g->workspace % 16 != 0)
     return kw_set_error_msg(KW_EINVAL, "kw_dec_lm_greedy: needs a zero-filled workspace of kw_dec_lm_greedy_workspace()");
   const DecP p = decp_from_args(a);  // (a fragment-major x: M <= 32, kw_dec_lm_greedy_supported)
@@ -1492,16 +1247,16 @@ extern "C" int kw_dec_lm_greedy(const kw_dec_linear_args* a, const kw_sampler_ar
   sg.arrive = reinterpret_cast<int*>(g->workspace);
   sg.fin = reinterpret_cast<int*>(g->workspace) + 32;
   sg.part = reinterpret_cast<unsigned long long*>(reinterpret_cast<char*>(g->workspace) + 256);
-  const int nkt = (int)(a->K / 32), nwv = (nkt + LMH_KTM - 1) / LMH_KTM;
-  hipLaunchKernelGGL(lm_head_kernel<true>, dim3((unsigned)lmg_grid(a->N)), dim3((unsigned)(64 * nwv)), 0,
-                     (hipStream_t)stream, p, lmh_groups_per_wg(a->N), sg);
+  const LmhGeo lg = lmh_geo(a->N, (int)(a->K / 32));
+  hipLaunchKernelGGL(lm_head_kernel<true>, dim3((unsigned)lg.grid), dim3((unsigned)(64 * lg.waves)), 0,
+                     (hipStream_t)stream, p, lg.per_wg, sg);
   KW_CHECK_LAUNCH();
   return KW_OK;
 }
 
 extern "C" size_t kw_dec_linear_workspace_bytes(int64_t N, int64_t K) {
   const Geo g = choose(N, K);
-  const int64_t ncg = (N + 16 * g.ncb - 1) / (16 * g.ncb);
+  const int64_t ncg = col_groups(N, g.ncb);
   return (size_t)CNT_MAX * sizeof(int) + (g.ks > 1 ? (size_t)ZMAX * ncg * g.ks * g.ncb * 512 * sizeof(float) : 0);
 }
 
@@ -1530,7 +1285,7 @@ extern "C" int kw_dec_linear(const kw_dec_linear_args* a, kw_stream_t stream) {
   const int nkt = (int)(a->K / 32);
   if ((nkt + g.ks * g.nw - 1) / (g.ks * g.nw) > g.ktm || g.ks > KSMAX || (a->ln && g.ks > 1))
     return kw_set_error_msg(KW_EUNSUPPORTED, "kw_dec_linear: K too long for the k-tile budget");
-  const int64_t ncg = (a->N + 16 * g.ncb - 1) / (16 * g.ncb);
+  const int64_t ncg = col_groups(a->N, g.ncb);
   if (g.ks > 1) {
     if (ncg * ZMAX > CNT_MAX) return kw_set_error_msg(KW_EINVAL, "kw_dec_linear: split-K needs N <= 8192");
     if (!a->workspace || a->ws_bytes < kw_dec_linear_workspace_bytes(a->N, a->K))
@@ -1542,7 +1297,8 @@ extern "C" int kw_dec_linear(const kw_dec_linear_args* a, kw_stream_t stream) {
   const bool lm_shape = a->ln && epi == KW_EPI_STORE && a->c_dtype == KW_DT_F32 && a->N >= 8192 && !a->gelu &&
                         a->scale_cols == 0;
   // a fragment-major x is read by dec_linear_kernel and the persistent LM head: <= 32 rows (one or two row tiles)
-  if (xtiled && (a->M > 32 || (lm_shape && !lmh_fits(a->M, a->N, nkt))))
+  const LmhGeo lg = lmh_geo(a->N, nkt);
+  if (xtiled && (a->M > 32 || (lm_shape && !lmh_fits(a->M, lg))))
     return kw_set_error_msg(KW_EINVAL, "kw_dec_linear: a KW_LD_TILED x needs M <= 32 (LM head: a shape lm_head_kernel covers)");
   if (lm_shape && a->M > LMH_MAX_ROWS && a->M <= LMR_MAXROWS && nkt % 8 == 0) {
     const DecP p = decp_from_args(a);
@@ -1558,17 +1314,12 @@ extern "C" int kw_dec_linear(const kw_dec_linear_args* a, kw_stream_t stream) {
     const hipError_t e = hipGetLastError();
     return e == hipSuccess ? KW_OK : kw_set_error(e);
   }
-  const bool lmh = lm_shape && lmh_fits(a->M, a->N, nkt);
+  const bool lmh = lm_shape && lmh_fits(a->M, lg);
   // rows: one launch with a grid z-slice per 32-row chunk (K-split launches: up to ZMAX chunks each)
   const int64_t step = (g.ks == 1 || lmh) ? a->M : 32 * ZMAX;
   for (int64_t m0 = 0; m0 < a->M; m0 += step) {
-    DecP p = decp_from_args(a);  // rows [m0, m0 + step) of it
-    p.M = (int)(a->M - m0 < step ? a->M - m0 : step);
-    p.x += m0 * a->ldx;
     const size_t csz = a->c_dtype == KW_DT_F32 ? 4 : 2;
-    if (p.C) p.C = reinterpret_cast<char*>(p.C) + m0 * a->ldc * csz;
-    if (p.h) p.h += m0 * a->ldh;
-    if (p.hb) p.hb += m0 * a->ldh;
+    DecP p = rows_window(decp_from_args(a), (int)m0, (int)step, csz);
     p.cnt = reinterpret_cast<int*>(a->workspace);
     p.slab = a->workspace ? reinterpret_cast<float*>(reinterpret_cast<char*>(a->workspace) + CNT_MAX * sizeof(int)) : nullptr;
     p.xlds = !xtiled && use_xlds(a->N, g) ? 1 : 0;
@@ -1578,11 +1329,8 @@ extern "C" int kw_dec_linear(const kw_dec_linear_args* a, kw_stream_t stream) {
                      ? a->ldh % 8 == 0 && (uintptr_t)p.h % 16 == 0 && (uintptr_t)p.hb % 16 == 0
                      : (a->ldc * (int64_t)csz) % 16 == 0 && (uintptr_t)p.C % 16 == 0);
     if (lmh) {
-      const int groups = (int)((a->N + 16 * LMH_NCB - 1) / (16 * LMH_NCB));
-      const int per = lmh_groups_per_wg(a->N);
-      const int nwv = (nkt + LMH_KTM - 1) / LMH_KTM;
-      hipLaunchKernelGGL(lm_head_kernel<false>, dim3((unsigned)((groups + per - 1) / per), 1, (unsigned)((p.M + 31) / 32)),
-                         dim3((unsigned)(64 * nwv)), 0, s, p, per, LmGreedy{});
+      hipLaunchKernelGGL(lm_head_kernel<false>, dim3((unsigned)lg.grid, 1, (unsigned)((p.M + 31) / 32)),
+                         dim3((unsigned)(64 * lg.waves)), 0, s, p, lg.per_wg, LmGreedy{});
       const hipError_t e = hipGetLastError();
       if (e != hipSuccess) return kw_set_error(e);
       continue;

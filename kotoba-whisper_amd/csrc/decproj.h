@@ -9,6 +9,7 @@
 // through LDS, as the launch reduces its waves.  A fragments come straight from the activation rows (L2), or from a
 // fragment-major copy of them (KW_LD_TILED).
 #pragma once
+#include "declin_tile.h"
 #include "kw_common.h"
 
 // development hook (tools/lab/qkv_stamps.hip defines it to record s_memrealtime per workgroup phase); no-op here
@@ -66,9 +67,6 @@ __device__ __forceinline__ void proj_publish_granules(const ProjArgs& a, int cg,
   // the fault-injection word, loaded by every workgroup (unconditionally: no phi on a loaded value) with the
   // epilogue constants; only workgroup 0 acts on it (kw_dec_*_status_offset in include/kwhisper.h)
   const int fault = __hip_atomic_load(a.fault, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  bf16x8 ones;
-#pragma unroll
-  for (int e = 0; e < 8; ++e) ones[e] = (__bf16)1.0f;
   // both virtual waves' weights in flight at once (HBM: the long round trip)
   bf16x8 wv[2][PROJ_KTM];
 #pragma unroll
@@ -103,35 +101,16 @@ __device__ __forceinline__ void proj_publish_granules(const ProjArgs& a, int cg,
     const int kt0 = (nkt * v) / nv, kt1 = (nkt * (v + 1)) / nv;
     const bf16x8* w = wv[r];
     if (!ONESHOT && r) load_a(1);
-    const bf16x8* a0 = av[r][0];
-    const bf16x8* a1 = av[r][1];
-    f32x4 c0 = f32x4{0.f, 0.f, 0.f, 0.f}, c1 = c0, s0 = c0, s1 = c0, q0 = c0, q1 = c0;
+    const bf16x8(&a0)[PROJ_KTM] = av[r][0];
+    const bf16x8(&a1)[PROJ_KTM] = av[r][1];
+    f32x4 c0 = f32x4{0.f, 0.f, 0.f, 0.f}, c1 = c0;
 #pragma unroll
     for (int u = 0; u < PROJ_KTM; ++u)
       if (kt0 + u < kt1) {
         c0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[u], w[u], c0, 0, 0, 0);
         c1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[u], w[u], c1, 0, 0, 0);
       }
-#pragma unroll
-    for (int u = 0; u < PROJ_KTM; ++u)
-      if (kt0 + u < kt1) {
-        s0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[u], ones, s0, 0, 0, 0);
-        s1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[u], ones, s1, 0, 0, 0);
-        q0 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a0[u], a0[u], q0, 0, 0, 0);
-        q1 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(a1[u], a1[u], q1, 0, 0, 0);
-      }
-    if ((lane & 15) == 0) {  // row sums: every column of x.1 holds them
-#pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        rpart[v][4 * (lane >> 4) + i][0] = s0[i];
-        rpart[v][16 + 4 * (lane >> 4) + i][0] = s1[i];
-      }
-    }
-    const int di = (lane & 15) - 4 * (lane >> 4);  // row sums of squares: the diagonal of x.x^T
-    if (di >= 0 && di < 4) {
-      rpart[v][lane & 15][1] = q0[di];
-      rpart[v][16 + (lane & 15)][1] = q1[di];
-    }
+    ln_row_partials<PROJ_KTM, true>(a0, a1, kt0, kt1, lane, rpart[v]);
     red[v][0][lane] = c0;
     red[v][1][lane] = c1;
   }
@@ -144,21 +123,8 @@ __device__ __forceinline__ void proj_publish_granules(const ProjArgs& a, int cg,
   const int hh = wave;
   f32x4 c = red[0][hh][lane];
   for (int v = 1; v < nv; ++v) c += red[v][hh][lane];
-  if (lane < 16) {
-    const int m = 16 * hh + lane;
-    float sx = 0.f, sq = 0.f;
-    for (int v = 0; v < nv; ++v) {
-      sx += rpart[v][m][0];
-      sq += rpart[v][m][1];
-    }
-    const float inv = 1.f / (float)a.K;
-    const float mean = sx * inv;
-    rstat[m][0] = mean;
-    rstat[m][1] = rsqrtf(fmaxf(sq * inv - mean * mean, 0.f) + a.ln_eps);
-  }
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+  if (lane < 16) ln_finish_row(rpart, nv, 16 * hh + lane, a.K, a.ln_eps, rstat);
+  wave_lds_sync();
   const int n = cg * 16 + (lane & 15);
   const bool drop = cg == 0 && fault != 0;  // test hook: this launch's consumers of columns [0, 16) time out
   if (drop && wave == 0 && lane == 0) __hip_atomic_store(a.fault, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -166,7 +132,7 @@ __device__ __forceinline__ void proj_publish_granules(const ProjArgs& a, int cg,
   for (int r = 0; r < 4; ++r) {
     const int m = 16 * hh + 4 * (lane >> 4) + r;
     float v = c[r];
-    v = rstat[m][1] * (v - rstat[m][0] * ecsum);
+    v = ln_fold(v, rstat[m][0], rstat[m][1], ecsum);
     v += ebias;
     if (n < a.scale_cols) v *= a.scale;
     const uint32_t mine = f2bf(v);

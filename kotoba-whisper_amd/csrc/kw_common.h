@@ -66,6 +66,14 @@ __device__ __forceinline__ void raw_barrier() {
   asm volatile("" ::: "memory");
 }
 
+// one wave's LDS writes made visible to its own other lanes: release fence, wave barrier, acquire fence (LDS is in
+// order within a wave; this keeps the compiler from moving the reads above the writes)
+__device__ __forceinline__ void wave_lds_sync() {
+  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+  __builtin_amdgcn_wave_barrier();
+  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
 template <typename T> struct TypeIO;
 template <> struct TypeIO<float> {
   static __device__ __forceinline__ float ld(const float* p) { return *p; }

@@ -1065,6 +1065,34 @@ def test_xq_cross_rejects_what_it_does_not_cover():
     assert not ops.xq_cross_supported(4, 1536, 24, 1500)   # K beyond dec_linear's 8 waves x 5 k-tiles
 
 
+def test_lm_greedy_rejects_a_generation_longer_than_its_eos_scan():
+    """kw_dec_lm_greedy looks for a row's earlier EOS in the 448 positions after begin_index: max_length -
+    begin_index = 448 runs, 449 is KW_EUNSUPPORTED (a RuntimeError on either backend) and launches nothing."""
+    B, V, K, P = 2, 8192, 64, 3
+    Wp = ops.pack_weight(torch.zeros(V, K, device="cuda", dtype=torch.bfloat16))
+    ids = torch.zeros((B, 512), dtype=torch.int64, device="cuda")
+    cur = torch.tensor([P], dtype=torch.int32, device="cuda")
+    unf = torch.ones(B, dtype=torch.int32, device="cuda")
+    nun = torch.zeros(1, dtype=torch.int32, device="cuda")
+    ws = torch.zeros(ops.lm_greedy_workspace_bytes(B, V) // 4 + 1, device="cuda")
+
+    def plan(max_length):
+        return ops.LmGreedyPlan(torch.zeros(B, K, device="cuda", dtype=torch.bfloat16), Wp, B, V, K,
+                                ln=(1e-5, torch.zeros(V, device="cuda")), bias=None,
+                                suppress_mask=torch.zeros(V, dtype=torch.uint8, device="cuda"), begin_suppress=None,
+                                ids=ids, cur_len=cur, unfinished=unf, n_unfinished=nun, eos_id=7000, pad_id=6999,
+                                max_length=max_length, begin_index=P, workspace=ws)
+
+    assert ops.lm_greedy_supported(B, V, K)
+    with pytest.raises(RuntimeError, match="max_length"):
+        plan(P + 449)()
+    torch.cuda.synchronize()
+    assert int(cur.item()) == P
+    plan(P + 448)()
+    torch.cuda.synchronize()
+    assert int(cur.item()) == P + 1
+
+
 def test_qkv_self_rejects_what_it_does_not_cover():
     assert not ops.qkv_self_supported(33, 1280, 20)  # more rows than one 32-row tile
     assert not ops.qkv_self_supported(4, 1280, 16)   # head_dim != 64

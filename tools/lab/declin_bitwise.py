@@ -1,7 +1,9 @@
 #!/usr/bin/env python
 """Lab (not product): kw_dec_linear outputs on fixed seeded inputs for every decode-step shape (o / xo, fc1, fc2 with its
-K-split seam, qkv, xq, LM head) at several row counts, saved to an npz -- run once per library (KWHISPER_LIB /
-KWHISPER_TORCH_LIB) and compare: a restructured epilogue or seam must give the same bits.
+K-split seam, qkv, xq, LM head) at several row counts -- row-major and, up to 32 rows, fragment-major (KW_LD_TILED x,
+KW_EPI_HB_TILED hb), kw_dec_lm_greedy's ids / cur_len / unfinished, the K-split at 257 rows -- saved to an npz: run
+once per library (KWHISPER_LIB / KWHISPER_TORCH_LIB) and compare: a restructured epilogue or seam must give the same
+bits.
 
     python tools/lab/declin_bitwise.py out.npz            # dump
     python tools/lab/declin_bitwise.py --compare a.npz b.npz
@@ -46,6 +48,48 @@ def dump(path):
                 ops.DecLinearPlan(x, Wp, M, N, K, ln=(1e-5, cs), bias=b, C=C, gelu=mode == "gelu", workspace=ws,
                                   scale=0.125 if mode == "ln" else 1.0, scale_cols=1280 if mode == "ln" else 0)()
                 out[f"{name}_{M}_C"] = (C.view(torch.int16) if dt == torch.bfloat16 else C).cpu().numpy()
+            if M <= 32:  # the fragment-major variants: x read tiled (KW_LD_TILED), hb written tiled (KW_EPI_HB_TILED)
+                xt = ops.act_tile(x)
+                if mode == "resid":
+                    hh = h.clone()
+                    hbt = torch.zeros(16 * ((M + 15) // 16), N, device="cuda", dtype=torch.bfloat16)
+                    ops.DecLinearPlan(xt, Wp, M, N, K, ldx=ops.KW_LD_TILED, bias=b, resid=(hh, hbt, N, 0), workspace=ws,
+                                      hb_tiled=True)()
+                    out[f"{name}_{M}_xt_h"] = hh.cpu().numpy()
+                    out[f"{name}_{M}_xt_hbt"] = hbt.view(torch.int16).cpu().numpy()
+                else:
+                    C = torch.empty(M, N, device="cuda", dtype=dt)
+                    ops.DecLinearPlan(xt, Wp, M, N, K, ldx=ops.KW_LD_TILED, ln=(1e-5, cs), bias=b, C=C,
+                                      gelu=mode == "gelu", workspace=ws, scale=0.125 if mode == "ln" else 1.0,
+                                      scale_cols=1280 if mode == "ln" else 0)()
+                    out[f"{name}_{M}_xt_C"] = (C.view(torch.int16) if dt == torch.bfloat16 else C).cpu().numpy()
+                if mode == "lm":  # kw_dec_lm_greedy: three steps' ids / cur_len / unfinished
+                    V, P = N, 3
+                    ids = torch.zeros((M, 64), dtype=torch.int64, device="cuda")
+                    cur = torch.tensor([P], dtype=torch.int32, device="cuda")
+                    unf = torch.ones(M, dtype=torch.int32, device="cuda")
+                    nun = torch.zeros(1, dtype=torch.int32, device="cuda")
+                    sup = torch.zeros(V, dtype=torch.uint8, device="cuda")
+                    sup[::7] = 1
+                    xg = x.clone()
+                    plan = ops.LmGreedyPlan(xg, Wp, M, V, K, ln=(1e-5, cs), bias=b, suppress_mask=sup,
+                                            begin_suppress=torch.tensor([220, 50257], dtype=torch.int32, device="cuda"),
+                                            ids=ids, cur_len=cur, unfinished=unf, n_unfinished=nun, eos_id=50257,
+                                            pad_id=50256, max_length=P + 3, begin_index=P,
+                                            workspace=torch.zeros(ops.lm_greedy_workspace_bytes(M, V) // 4 + 1, device="cuda"))
+                    for step in range(3):
+                        xg.copy_(torch.roll(x, step, 1))
+                        plan()
+                    out[f"{name}_{M}_greedy_ids"] = ids.cpu().numpy()
+                    out[f"{name}_{M}_greedy_state"] = torch.cat([cur, nun, unf]).cpu().numpy()
+        if name == "fc2":  # K-split at 257 rows: a second 32 * ZMAX window of the seam
+            M = 257
+            x = (torch.randn(M, K, device="cuda", generator=g) * 2 + 0.3).bfloat16()
+            h = torch.randn(M, N, device="cuda", generator=g)
+            hb = torch.empty(M, N, device="cuda", dtype=torch.bfloat16)
+            ops.DecLinearPlan(x, Wp, M, N, K, bias=b, resid=(h, hb, N, 0), workspace=ws)()
+            out[f"{name}_{M}_h"] = h.cpu().numpy()
+            out[f"{name}_{M}_hb"] = hb.view(torch.int16).cpu().numpy()
     # decode attention (r06: the cross / self helpers' reductions restructured): the pair kernel (B = 32), the chunk
     # grid (B = 2), the fused query projection, multi-row cross-attention (prefill / beams), the fused self block and
     # the plain self-attention step at several lengths

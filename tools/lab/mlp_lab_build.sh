@@ -7,6 +7,9 @@
 # KW_BEAM_LAB_* (beam top-k sweeps) -- plus an optional second patch, compiled with the given defines, so the product
 # sources (and the kernel-source hash the committed PMC profiles carry) stay untouched.
 #   bash tools/lab/mlp_lab_build.sh ["-DKW_LAB_MLP -DKW_LAB_OVERRIDES ..."] [extra.diff]
+# (lab_switches.diff, mlp_lab.diff and fc2_rowsplit.diff were cut against declin.hip as it stood before its tile steps
+# moved into declin_tile.h and its helpers: their declin.hip hunks no longer apply and would have to be redone against
+# the helpers.  They are kept as the record of what was measured.)
 set -e
 ROOT="$(cd "$(dirname "$0")/../.." && pwd)"
 T=/tmp/kw_mlp_lab_src
