@@ -403,6 +403,45 @@ typedef struct {
 
 int kw_beam_select(const kw_beam_select_args* args, kw_stream_t stream);
 
+/* ---- token-level timestamps (additive, ABI 112 unchanged) --------------------------------------------
+ * return_token_timestamps: WhisperGenerationMixin._extract_token_timestamps, _median_filter and
+ * _dynamic_time_warping (TF/models/whisper/generation_whisper.py:241-381, 43-61, 64-115) on device.
+ * Head dimension 64.  `heads`, `slots` and `pairs` below are HOST arrays, read (and range-checked) at the call. */
+
+/* One decode step's log entry.  q: [B][d] (dtype), the scaled cross-attention queries of one layer for the step whose
+ * position the device cur_len names; for i < n (<= 32) the 64-wide slice of head heads[i] of every row is copied to
+ * log[slots[i]][b][t][0..63], log: [n_slots][B][t_log][64] (dtype), t = cur_len - 1 - begin_index (the index of the
+ * step's input token among the generated ones); steps with t outside [0, t_log) write nothing. */
+int kw_align_capture(int dtype, const void* q, int64_t B, int64_t d, const int32_t* heads, const int32_t* slots,
+                     int64_t n, int64_t n_slots, const int32_t* cur_len, int64_t begin_index, void* log, int64_t t_log,
+                     kw_stream_t stream);
+
+/* out[a][b][t][s] = softmax_s(qlog[a][b][t] . k_cache[pairs[a][0]][b][pairs[a][1]][s]) for t < T, a < A (<= 32 per
+ * call), f32 accumulation and output.  qlog: [A][B][t_log][64], k_cache: layer l's keys [B][H][S][64] at
+ * k_cache + l * k_layer_stride elements (both dtype, 16-B aligned); pairs: [A][2] (layer < n_layers, head < H);
+ * out: [A][B][T][S] f32 (TF modeling_whisper.py:323-356 with scaling 1.0, the queries being scaled already). */
+int kw_align_weights(int dtype, const void* qlog, int64_t t_log, const void* k_cache, int64_t k_layer_stride,
+                     int64_t n_layers, const int32_t* pairs, int64_t A, int64_t B, int64_t H, int64_t S, int64_t T,
+                     float* out, kw_stream_t stream);
+
+/* weights [A][B][T][S] f32 -> the DTW matrix out [B][T][S] f32: each (a, b, frame) column z-scored over the T steps
+ * (population std; a zero std gives NaN as in torch), a median filter of odd filter_width (<= 15) along the frames with
+ * reflect padding over the row's first frames[b] frames (device int32 [B], NULL = S; skipped when that count is
+ * <= filter_width / 2), the mean over the pairs, negated.  Columns >= frames[b] are written as 0.  More than 32 pairs
+ * go in chunks: each call adds its A pairs (first != 0 starts from zero), the call with last != 0 divides by a_total
+ * and negates. */
+int kw_align_reduce(const float* weights, int64_t A, int64_t B, int64_t T, int64_t S, const int32_t* frames,
+                    int64_t filter_width, float* out, int64_t a_total, int first, int last, kw_stream_t stream);
+
+/* _dynamic_time_warping + the text-index jumps of its path, one workgroup per row: matrix [B][T][S] f32 (row b uses
+ * its first frames[b] columns; device int32 [B], NULL = S), T <= 1024.  out[b][t] (int32) = the frame index at which
+ * the path first reaches step t (the reference's time_indices[jumps]; -1 where the path reaches the step before any
+ * frame).  float32 cost, the reference's tie rule with plain IEEE `<`.  workspace: >= kw_dtw_workspace(B, T, S) bytes
+ * (the trace, one byte per cell). */
+int kw_dtw(const float* matrix, int64_t B, int64_t T, int64_t S, const int32_t* frames, int32_t* out, void* workspace,
+           size_t ws_bytes, kw_stream_t stream);
+size_t kw_dtw_workspace(int64_t B, int64_t T, int64_t S);
+
 #ifdef __cplusplus
 }
 #endif

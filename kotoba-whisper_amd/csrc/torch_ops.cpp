@@ -435,6 +435,75 @@ void beam_select(const Tensor& cand_val, const Tensor& cand_idx, Tensor& ids, op
   check(kw_beam_select(&a, stream_of(ids)), w);
 }
 
+// ---- token-level timestamps ---------------------------------------------------------------------------
+std::vector<int32_t> i32(const std::vector<int64_t>& v) { return std::vector<int32_t>(v.begin(), v.end()); }
+
+void align_capture(const Tensor& q, std::vector<int64_t> heads, std::vector<int64_t> slots, const Tensor& cur_len,
+                   int64_t begin_index, Tensor& log) {
+  const char* w = "kw_align_capture";
+  dev(q, w), dev(cur_len, w), dev(log, w);
+  TORCH_CHECK_VALUE(q.dim() == 2 && q.is_contiguous() && log.dim() == 4 && log.is_contiguous() && log.size(3) == 64 &&
+                        log.size(1) == q.size(0) && log.scalar_type() == q.scalar_type() && heads.size() == slots.size(),
+                    "kw_align_capture: q [B][d], log [A][B][t_log][64] of q's dtype, one slot per head");
+  const auto h = i32(heads), sl = i32(slots);
+  c10::DeviceGuard g(q.device());
+  check(kw_align_capture(dt_of(q), ptr(q), q.size(0), q.size(1), h.data(), sl.data(), (int64_t)h.size(), log.size(0),
+                         ptr<const int32_t>(cur_len), begin_index, ptr(log), log.size(2), stream_of(q)),
+        w);
+}
+
+// qlog [A_all][B][t_log][64] and k_cache [n_layers'][B][H][S][64] (layer l's keys at index l * layer_step); the call
+// covers pairs a0 .. a0 + A - 1 of qlog (pairs: their (layer, head), flattened)
+void align_weights(const Tensor& qlog, int64_t a0, const Tensor& k_cache, int64_t layer_step, std::vector<int64_t> pairs,
+                   int64_t T, Tensor& out) {
+  const char* w = "kw_align_weights";
+  dev(qlog, w), dev(k_cache, w), dev(out, w);
+  const int64_t A = (int64_t)pairs.size() / 2;
+  TORCH_CHECK_VALUE(qlog.dim() == 4 && qlog.is_contiguous() && k_cache.dim() == 5 && k_cache.is_contiguous() &&
+                        k_cache.size(4) == 64 && qlog.size(3) == 64 && k_cache.scalar_type() == qlog.scalar_type() &&
+                        k_cache.size(1) == qlog.size(1) && pairs.size() % 2 == 0 && a0 >= 0 && a0 + A <= qlog.size(0) &&
+                        layer_step >= 1,
+                    "kw_align_weights: qlog [A][B][t_log][64], k_cache [n][B][H][S][64] of one dtype");
+  const int64_t B = qlog.size(1), H = k_cache.size(2), S = k_cache.size(3);
+  TORCH_CHECK_VALUE(out.scalar_type() == at::kFloat && out.is_contiguous() && out.numel() >= A * B * T * S,
+                    "kw_align_weights: out must be a contiguous float32 tensor of A * B * T * S elements");
+  const auto p = i32(pairs);
+  c10::DeviceGuard g(qlog.device());
+  check(kw_align_weights(dt_of(qlog), ptr(qlog, a0 * B * qlog.size(2) * 64), qlog.size(2), ptr(k_cache),
+                         layer_step * k_cache.stride(0), (k_cache.size(0) + layer_step - 1) / layer_step, p.data(), A, B,
+                         H, S, T, ptr<float>(out), stream_of(qlog)),
+        w);
+}
+
+void align_reduce(const Tensor& weights, int64_t A, int64_t B, int64_t T, int64_t S, const optional<Tensor>& frames,
+                  int64_t filter_width, Tensor& out, int64_t a_total, int64_t first, int64_t last) {
+  const char* w = "kw_align_reduce";
+  dev(weights, w), dev(frames, w), dev(out, w);
+  TORCH_CHECK_VALUE(weights.scalar_type() == at::kFloat && weights.is_contiguous() && out.scalar_type() == at::kFloat &&
+                        out.is_contiguous() && A > 0 && B > 0 && T > 0 && S > 0 && weights.numel() >= A * B * T * S &&
+                        out.numel() >= B * T * S &&
+                        (!frames.has_value() || (frames->scalar_type() == at::kInt && frames->numel() >= B)),
+                    "kw_align_reduce: weights [A][B][T][S] f32, out [B][T][S] f32, frames int32 [B]");
+  c10::DeviceGuard g(weights.device());
+  check(kw_align_reduce(ptr<const float>(weights), A, B, T, S, optr<const int32_t>(frames), filter_width, ptr<float>(out),
+                        a_total, (int)first, (int)last, stream_of(weights)),
+        w);
+}
+
+void dtw(const Tensor& matrix, const optional<Tensor>& frames, Tensor& out, Tensor& workspace) {
+  const char* w = "kw_dtw";
+  dev(matrix, w), dev(frames, w), dev(out, w), dev(workspace, w);
+  TORCH_CHECK_VALUE(matrix.dim() == 3 && matrix.is_contiguous() && matrix.scalar_type() == at::kFloat &&
+                        out.scalar_type() == at::kInt && out.is_contiguous() &&
+                        out.numel() >= matrix.size(0) * matrix.size(1) &&
+                        (!frames.has_value() || (frames->scalar_type() == at::kInt && frames->numel() >= matrix.size(0))),
+                    "kw_dtw: matrix [B][T][S] f32, out int32 [B][T], frames int32 [B]");
+  c10::DeviceGuard g(matrix.device());
+  check(kw_dtw(ptr<const float>(matrix), matrix.size(0), matrix.size(1), matrix.size(2), optr<const int32_t>(frames),
+               ptr<int32_t>(out), ptr(workspace), (size_t)workspace.numel() * workspace.element_size(), stream_of(matrix)),
+        w);
+}
+
 // ---- workspace / packing sizes (host queries) ---------------------------------------------------------
 int64_t workspace_bytes(std::string kind, std::vector<int64_t> d) {
   auto n = [&](size_t i) { return at_(d, i, "kw::workspace_bytes"); };
@@ -447,6 +516,7 @@ int64_t workspace_bytes(std::string kind, std::vector<int64_t> d) {
   if (kind == "qkv_self") return (int64_t)kw_dec_qkv_self_workspace(n(0), n(1));
   if (kind == "xq_cross") return (int64_t)kw_dec_xq_cross_workspace(n(0), n(1), n(2), n(3));
   if (kind == "beam_logprobs") return (int64_t)kw_beam_logprobs_workspace(n(0));
+  if (kind == "dtw") return (int64_t)kw_dtw_workspace(n(0), n(1), n(2));
   // byte offsets of the hand-off status words inside those workspaces (include/kwhisper.h)
   if (kind == "qkv_self_status") return (int64_t)kw_dec_qkv_self_status_offset(n(0), n(1));
   if (kind == "xq_cross_status") return (int64_t)kw_dec_xq_cross_status_offset(n(0), n(1), n(2), n(3));
@@ -491,6 +561,11 @@ TORCH_LIBRARY(kw, m) {
         "Tensor(d!) fin_seq, Tensor(e!) fin_score, Tensor(f!) fin_len, Tensor(g!) fin_flag, Tensor(h!) unsat, "
         "Tensor(i!) cur_len, Tensor(j!) counter, Tensor(k!) go, Tensor(l!) done, Tensor(m!) item_flags, int[] cfg, "
         "float length_penalty) -> ()");
+  m.def("align_capture(Tensor q, int[] heads, int[] slots, Tensor cur_len, int begin_index, Tensor(a!) log) -> ()");
+  m.def("align_weights(Tensor qlog, int a0, Tensor k_cache, int layer_step, int[] pairs, int T, Tensor(a!) out) -> ()");
+  m.def("align_reduce(Tensor weights, int A, int B, int T, int S, Tensor? frames, int filter_width, Tensor(a!) out, "
+        "int a_total, int first, int last) -> ()");
+  m.def("dtw(Tensor matrix, Tensor? frames, Tensor(a!) out, Tensor(b!) workspace) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(kw, CUDA, m) {
@@ -510,4 +585,8 @@ TORCH_LIBRARY_IMPL(kw, CUDA, m) {
   m.impl("dec_lm_greedy", &dec_lm_greedy);
   m.impl("beam_logprobs", &beam_logprobs);
   m.impl("beam_select", &beam_select);
+  m.impl("align_capture", &align_capture);
+  m.impl("align_weights", &align_weights);
+  m.impl("align_reduce", &align_reduce);
+  m.impl("dtw", &dtw);
 }

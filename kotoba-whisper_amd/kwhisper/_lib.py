@@ -21,7 +21,7 @@ TORCH_LIB_PATH = os.environ.get("KWHISPER_TORCH_LIB") or os.path.join(os.path.di
                                                                       "libkwhisper_torch.so")
 TORCH_OPS = ("log_mel", "mel_to_time_major", "gemm", "dec_linear", "pack_weight", "layernorm", "attention", "embed",
              "self_attn_step", "dec_qkv_self", "dec_xq_cross", "cross_attn_step", "greedy_step", "dec_lm_greedy",
-             "beam_logprobs", "beam_select")
+             "beam_logprobs", "beam_select", "align_capture", "align_weights", "align_reduce", "dtw")
 
 KW_OK, KW_EINVAL, KW_EHIP, KW_EUNSUPPORTED = 0, 1, 2, 3
 KW_DT_F32, KW_DT_BF16 = 0, 1
@@ -151,6 +151,14 @@ EXPORTS = {
     "kw_beam_logprobs": (ctypes.c_int, [ctypes.POINTER(BeamLogprobsArgs), c_vp]),
     "kw_beam_logprobs_workspace": (ctypes.c_size_t, [c_i64]),
     "kw_beam_select": (ctypes.c_int, [ctypes.POINTER(BeamSelectArgs), c_vp]),
+    "kw_align_capture": (ctypes.c_int, [ctypes.c_int, c_vp, c_i64, c_i64, ctypes.POINTER(c_i32), ctypes.POINTER(c_i32),
+                                        c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp]),
+    "kw_align_weights": (ctypes.c_int, [ctypes.c_int, c_vp, c_i64, c_vp, c_i64, c_i64, ctypes.POINTER(c_i32), c_i64,
+                                        c_i64, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "kw_align_reduce": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_i64, c_vp, c_i64, ctypes.c_int,
+                                       ctypes.c_int, c_vp]),
+    "kw_dtw": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, ctypes.c_size_t, c_vp]),
+    "kw_dtw_workspace": (ctypes.c_size_t, [c_i64, c_i64, c_i64]),
 }
 
 _lib = None

@@ -73,6 +73,7 @@ class WhisperShape:
     eos_token_id: int = 50257
     bos_token_id: int = 50257
     layer_norm_eps: float = 1e-5
+    median_filter_width: int = 7  # token timestamps: the median filter over encoder frames (configuration_whisper.py)
 
     @property
     def head_dim(self) -> int:
@@ -135,6 +136,9 @@ class GenerationConstants:
     language: str | None = None
     task: str | None = None
     forced_decoder_ids: list | None = None
+    # [layer, head] pairs of the cross-attention heads token timestamps are read from (return_token_timestamps);
+    # None = the generation config has none (HF: the attribute is missing)
+    alignment_heads: list | None = None
 
     @property
     def timestamp_begin(self) -> int:
@@ -147,6 +151,7 @@ class GenerationConstants:
             begin_suppress_tokens=list(self.begin_suppress_tokens) if self.begin_suppress_tokens is not None else None,
             lang_to_id=dict(self.lang_to_id),
             task_to_id=dict(self.task_to_id),
+            alignment_heads=[list(p) for p in self.alignment_heads] if self.alignment_heads is not None else None,
         )
 
     def to_dict(self) -> dict:

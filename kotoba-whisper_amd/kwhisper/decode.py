@@ -73,6 +73,9 @@ class DecodeSession:
         self.logits = torch.empty((R, s.vocab_size), device=dev, dtype=torch.float32)
         self._bufs = {}
         self._plans = {}
+        self._align_logs = {}  # alignment pair set -> its query log (token timestamps)
+        self.align_out = None  # the last generate(align=...)'s alignment results
+        self.keep_alignment = False  # True: align_out also keeps the DTW matrix and the raw weights (validation)
         # split-K seam scratch shared by every decode linear of a step (stream-ordered; zeroed once)
         ws = 0
         if eng.packed:
@@ -134,7 +137,7 @@ class DecodeSession:
         v.eng, v.nb, v.B, v.R, v.T = self.eng, 1, r1 - r0, r1 - r0, self.T
         v.cross, v.kc, v.vc = self.cross[:, r0:r1], self.kc[:, r0:r1], self.vc[:, r0:r1]
         v.ids, v.bp, v.cur_len, v.logits = self.ids[r0:r1], None, self.cur_len, self.logits[r0:r1]
-        v._bufs, v._plans = {}, {}
+        v._bufs, v._plans, v._align_logs = {}, {}, {}
         v.lin_ws = torch.zeros_like(self.lin_ws) if self.lin_ws is not None else None
         v.self_ws = torch.zeros_like(self.self_ws)
         v.qs_ok = v.xc_ok = v.tiled_ok = False
@@ -202,16 +205,35 @@ class DecodeSession:
         """f32 parity-mode linear (kw_gemm)."""
         return [ops.GemmPlan(A, W, C, M, N, K, **kw)]
 
-    def _step_plans(self, q: int, fused: bool = False):
+    def _align_log(self, align):
+        """The query log [A][R][T_MAX][64] of the alignment pairs ``align``, kept for the session's lifetime: step
+        plans and captured graphs hold its address."""
+        log = self._align_logs.get(align)
+        if log is None:
+            log = self._align_logs[align] = torch.zeros((len(align), self.R, T_MAX, _HD), device=self.eng.device,
+                                                        dtype=self.eng.dtype)
+        return log
+
+    def _step_plans(self, q: int, fused: bool = False, align=None, begin_index: int = 0):
         """The decoder forward for q new positions per row (q = prompt length for the prefill, 1 after).
+        ``align`` (q == 1, greedy): the alignment (layer, head) pairs whose cross-attention queries every step logs
+        (kw_align_capture after the layer's query projection; such a layer takes the two-launch cross path, which
+        leaves the query in global memory and is bitwise the fused block).  None: exactly the plain plan.
         ``fused`` (q == 1): each layer's LayerNorm-fused QKV projection and self-attention step as ONE
         kw_dec_qkv_self launch (caches bitwise the two-launch plan's, attention within bf16 rounding) -- for steps at positions < 256 only."""
         fused = bool(fused and q == 1 and self.qs_ok)
-        key = (q, fused)
+        key = (q, fused) if align is None else (q, fused, align, begin_index)
         if key in self._plans:
             return self._plans[key]
         eng, s = self.eng, self.eng.shape
         b = self._buffers(q)
+        capture = {}  # layer -> the capture launch after its cross query projection
+        if align is not None:
+            log = self._align_log(align)
+            for li in sorted({l for l, _ in align}):
+                slots = [i for i, (l, _) in enumerate(align) if l == li]
+                capture[li] = ops.AlignCapturePlan(b["qx"], [align[i][1] for i in slots], slots, self.cur_len,
+                                                   begin_index, log)
         d, H, B = s.d_model, eng.H, self.R  # B: running rows
         rows = B * q
         scale = _HD ** -0.5
@@ -237,16 +259,19 @@ class DecodeSession:
                     seq.append(("self", q, b["qkv"], li, b["attn"]))
                 seq.append(lin(b["attn"], lay["o_w"], rows, d, d, bias=lay["o_b"], resid=(h, hb, d, 0), workspace=ws,
                                tag="o", hb_tiled=tiled, ldx=xld if fused else None))  # (the fused block's attn)
-                if q == 1 and self.xc_ok:
+                xc = q == 1 and self.xc_ok and li not in capture
+                if xc:
                     seq.append(ops.XqCrossPlan(hb, lay["xq_w"], rows, d, H, ln=(eps, lay["xq_cs"]), bias=lay["xq_b"],
                                                scale=scale, k=self.cross[2 * li], v=self.cross[2 * li + 1], S=self.T,
                                                out=b["attn"], workspace=self.xc_ws, ldx=xld))
                 else:
                     seq.append(lin(hb, lay["xq_w"], rows, d, d, ln=(eps, lay["xq_cs"]), bias=lay["xq_b"],
                                    C=b["qx"], scale=scale, scale_cols=d, workspace=ws, tag="xq", ldx=xld))
+                    if li in capture:
+                        seq.append(capture[li])
                     seq.append(("cross", q, b["qx"], li, b["attn"], b["ws"]))
                 seq.append(lin(b["attn"], lay["xo_w"], rows, d, d, bias=lay["xo_b"], resid=(h, hb, d, 0),
-                               workspace=ws, tag="xo", hb_tiled=tiled, ldx=xld if q == 1 and self.xc_ok else None))
+                               workspace=ws, tag="xo", hb_tiled=tiled, ldx=xld if xc else None))
                 seq.append(lin(hb, lay["fc1_w"], rows, s.decoder_ffn_dim, d, ln=(eps, lay["fc1_cs"]),
                                bias=lay["fc1_b"], C=b["ffn"], gelu=True, workspace=ws, tag="fc1", ldx=xld))
                 seq.append(lin(b["ffn"], lay["fc2_w"], rows, d, s.decoder_ffn_dim, bias=lay["fc2_b"],
@@ -265,6 +290,8 @@ class DecodeSession:
             seq += self._gemm(b["attn"], lay["o_w"], b["h"], rows, d, d, bias=lay["o_b"], epilogue=L.KW_EPI_RESID)
             seq.append(("ln", b["h"], lay["ln2_g"], lay["ln2_b"], b["x"]))
             seq += self._gemm(b["x"], lay["xq_w"], b["qx"], rows, d, d, bias=lay["xq_b"], scale=scale, scale_cols=d)
+            if li in capture:
+                seq.append(capture[li])
             seq.append(("cross", q, b["qx"], li, b["attn"], b["ws"]))
             seq += self._gemm(b["attn"], lay["xo_w"], b["h"], rows, d, d, bias=lay["xo_b"], epilogue=L.KW_EPI_RESID)
             seq.append(("ln", b["h"], lay["ln3_g"], lay["ln3_b"], b["x"]))
@@ -381,11 +408,26 @@ class DecodeSession:
         return False
 
     def generate(self, prompt: torch.Tensor, gen, *, max_length: int, return_timestamps: bool,
-                 check_every: int = 4, use_graph: bool = True, record_scores: bool = False):
+                 check_every: int = 4, use_graph: bool = True, record_scores: bool = False, align=None,
+                 num_frames=None, median_filter_width: int = 7):
         """Greedy loop of GenerationMixin._sample (TF/generation/utils.py:2783-2941).
 
         Returns host int64 ids (B, L) including the prompt, with L exactly the length the reference
-        loop stops at (all rows finished or max_length)."""
+        loop stops at (all rows finished or max_length).
+
+        ``align``: the alignment (layer, head) pairs of ``return_token_timestamps``.  Every step then logs those
+        heads' cross-attention queries, and after decoding the alignment stage (weights, normalisation, DTW) runs
+        on device over the steps the reference would have run; ``self.align_out["frames"]`` holds int32 (B, L - P - 1),
+        the encoder position of every step (``num_frames``: per-row feature frames, the crop of
+        TF generation_whisper.py:310-354, or None)."""
+        if align is not None:
+            align = tuple((int(l), int(h)) for l, h in align)
+            nl, nh = self.eng.shape.decoder_layers, self.eng.H
+            if not align or any(not (0 <= l < nl and 0 <= h < nh) for l, h in align):
+                raise ValueError(f"alignment_heads must be [layer, head] pairs within {nl} layers x {nh} heads")
+            if self.nb != 1:
+                raise NotImplementedError("token timestamps with beam search")
+        self.align_out = None
         B = self.B
         P = prompt.shape[1]
         if P + 1 > T_MAX + 1 or max_length > T_MAX:
@@ -402,7 +444,7 @@ class DecodeSession:
         key = (max_length, P, bool(return_timestamps), tuple(gen.suppress_tokens or ()),
                tuple(gen.begin_suppress_tokens or ()), gen.timestamp_begin, gen.no_timestamps_token_id,
                gen.eos_token_id, gen.pad_token_id, gen.max_initial_timestamp_index, bool(record_scores),
-               self.eng.prefill_streams, self.eng.fuse_lm_greedy)
+               self.eng.prefill_streams, self.eng.fuse_lm_greedy, align)
         cfg = self._greedy_cfg.get(key)
         if cfg is None:
             sup = torch.zeros((self.eng.shape.vocab_size,), dtype=torch.uint8)
@@ -445,7 +487,7 @@ class DecodeSession:
         n_steps = max_length - P  # tokens the reference can add at most
         done = 1
         fused = max_length <= 256  # every step's position < 256 (kw_dec_qkv_self's key range)
-        step_seq = self._step_plans(1, fused=fused)
+        step_seq = self._step_plans(1, fused=fused, align=align, begin_index=P)
         self.fused_last = bool(fused and self.qs_ok)
         # the step's LM head + greedy step as one launch (kw_dec_lm_greedy; no timestamps, no recorded scores)
         tail = sampler
@@ -515,7 +557,42 @@ class DecodeSession:
         self.check_handoffs()
         L_now = int(self.cur_len.item())
         ids = self.ids[:, :L_now].cpu().numpy()
-        return _reference_length(ids, P, gen.eos_token_id, max_length)
+        ids = _reference_length(ids, P, gen.eos_token_id, max_length)
+        if align is not None:
+            # the steps the reference ran: one per generated token but the last (not the poll lag's extra replays)
+            self.align_out = self._alignment(align, ids.shape[1] - P - 1, num_frames, median_filter_width)
+        return ids
+
+    def _alignment(self, align, T: int, num_frames, width: int):
+        """weights -> reduce -> DTW over the first ``T`` logged steps; the host receives (B, T) frame indices."""
+        B, S, dev = self.B, self.T, self.eng.device
+        if T <= 0:
+            return dict(frames=np.zeros((B, 0), np.int32), T=0)
+        log = self._align_log(align)
+        frames = None
+        if num_frames is not None:
+            # the reference crops with weights[..., : n // 2] (generation_whisper.py:354): a Python slice, so a
+            # negative n (a row whose mask ends before the pass's seek) keeps S + n // 2 positions
+            frames = torch.tensor([len(range(S)[: int(n) // 2]) for n in num_frames], dtype=torch.int32, device=dev)
+        A = len(align)
+        # pairs per chunk: the f32 weights of a chunk stay under 256 MB (and 32 pairs, the kernels' launch limit)
+        chunk = max(1, min(32, A, (256 << 20) // (B * T * S * 4)))
+        weights = torch.empty((chunk, B, T, S), device=dev, dtype=torch.float32)
+        matrix = torch.empty((B, T, S), device=dev, dtype=torch.float32)
+        kept = []
+        for a0 in range(0, A, chunk):
+            n = min(chunk, A - a0)
+            ops.align_weights(log, self.cross, align[a0: a0 + n], T, weights, a0=a0, layer_step=2)
+            ops.align_reduce(weights, n, B, T, S, frames, width, matrix, a_total=A, first=a0 == 0, last=a0 + n >= A)
+            if self.keep_alignment:
+                kept.append(weights[:n].clone())
+        out = ops.dtw(matrix, frames)
+        res = dict(frames=out.cpu().numpy(), T=T)
+        if self.keep_alignment:
+            res["matrix"] = matrix.cpu().numpy()
+            res["weights"] = torch.cat(kept).cpu().numpy()  # [A][B][T][S]
+            res["num_frames"] = None if frames is None else frames.cpu().numpy()
+        return res
 
 
     def generate_beam(self, prompt: torch.Tensor, gen, *, num_beams: int, max_length: int, return_timestamps: bool,

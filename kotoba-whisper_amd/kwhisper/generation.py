@@ -14,6 +14,8 @@ TF/models/whisper/generation_whisper.py:383-968):
   * segments and right padding with ``pad_token_id``                 :1977-2074, :126-237
   * ``return_dict_in_generate`` (no timestamps): sequences incl. prompt  :916-934
   * ``num_beams`` > 1: GenerationMixin._beam_search on device (TF/generation/utils.py:3208-3527)
+  * ``return_token_timestamps``: the alignment heads' cross-attention weights, their normalisation and the
+    dynamic time warping on device (csrc/token_ts.hip)                :241-381, :1146-1157, :1685-1700
 """
 from __future__ import annotations
 
@@ -82,6 +84,9 @@ class KWhisperForConditionalGeneration:
         # True: generate() also keeps every seek pass's decoded ids in stats["pass_ids"] (validation: a fixture of the
         # engine's own multi-pass trajectory, tools/dump_hipmel.py)
         self.record_pass_ids = False
+        # True: generate(return_token_timestamps=True) also keeps every pass's alignment results (frame indices, the
+        # DTW matrix, the raw weights) in stats["alignment"] (validation)
+        self.record_alignment = False
         self._memo = None  # generate_multitask's per-batch encoder memo
         self._memo_count = 0
 
@@ -132,6 +137,7 @@ class KWhisperForConditionalGeneration:
             decoder_layers=cfg["decoder_layers"], decoder_attention_heads=cfg["decoder_attention_heads"],
             decoder_ffn_dim=cfg["decoder_ffn_dim"], max_source_positions=cfg.get("max_source_positions", 1500),
             max_target_positions=cfg.get("max_target_positions", 448),
+            median_filter_width=cfg.get("median_filter_width", 7),
             decoder_start_token_id=cfg.get("decoder_start_token_id", 50258), pad_token_id=cfg.get("pad_token_id", 50256),
             eos_token_id=cfg.get("eos_token_id", 50257), bos_token_id=cfg.get("bos_token_id", 50257))
         sd = {}
@@ -166,7 +172,7 @@ class KWhisperForConditionalGeneration:
         if logits_processor or stopping_criteria:
             raise NotImplementedError("custom logits_processor / stopping_criteria are not supported on device")
         for k in ("prompt_ids", "prefix_allowed_tokens_fn", "compression_ratio_threshold", "logprob_threshold",
-                  "no_speech_threshold", "return_token_timestamps", "assistant_model"):
+                  "no_speech_threshold", "assistant_model"):
             if kwargs.get(k) is not None and kwargs.get(k) is not False:
                 raise NotImplementedError(f"`{k}` is not supported by the MI355X engine yet")
         if kwargs.get("temperature") not in (None, 0, 0.0) or kwargs.get("do_sample"):
@@ -185,6 +191,22 @@ class KWhisperForConditionalGeneration:
         max_length = kwargs.get("max_length", gen.max_length)
         s = self.engine.shape
         eng = self.engine
+        # token timestamps (_set_num_frames, generation_whisper.py:1685-1700)
+        token_ts = bool(kwargs.get("return_token_timestamps"))
+        align = ts_frames = None
+        if token_ts:
+            if getattr(gen, "alignment_heads", None) is None:
+                raise ValueError(
+                    "Model generation config has no `alignment_heads`, token-level timestamps not available. "
+                    "See https://gist.github.com/hollance/42e32852f24243b748ae6bc1f985b13a on how to add this property "
+                    "to the generation config.")
+            if num_beams > 1:
+                raise NotImplementedError(
+                    "`return_token_timestamps` with `num_beams` > 1 is not supported by the MI355X engine yet (the "
+                    "beam_indices gather of the cross-attention weights); use greedy decoding")
+            align = [tuple(p) for p in gen.alignment_heads]
+            if attention_mask is not None:
+                ts_frames = torch.as_tensor(attention_mask).sum(-1).cpu().long().numpy()
 
         enc_given = kwargs.get("encoder_outputs")
         if input_features is None and enc_given is None:
@@ -243,6 +265,7 @@ class KWhisperForConditionalGeneration:
         passes = 0
         row_passes = np.zeros(B, dtype=np.int64)
         pass_log, pass_ids = [], []  # per pass: (rows, their seek, their frame count); the decoded ids
+        align_log, last_ts = [], None
         while (seek < max_frames).any():
             batch_map = [p for p in batch_map if seek[p] < max_frames[p]]
             cur = len(batch_map)
@@ -285,6 +308,16 @@ class KWhisperForConditionalGeneration:
                 ids = sess.generate_beam(torch.from_numpy(prompt), gen, num_beams=num_beams, max_length=eff_max,
                                          return_timestamps=return_timestamps, length_penalty=length_penalty,
                                          early_stopping=early_stopping)
+            elif token_ts:
+                # per pass: num_frames - seek of the rows still running (generation_whisper.py:1146-1150)
+                nf = None if ts_frames is None else [int(ts_frames[p] - seek[p]) for p in batch_map]
+                sess.keep_alignment = self.record_alignment
+                ids = sess.generate(torch.from_numpy(prompt), gen, max_length=eff_max,
+                                    return_timestamps=return_timestamps, align=align, num_frames=nf,
+                                    median_filter_width=s.median_filter_width)
+                pass_ts = _pass_token_timestamps(sess.align_out["frames"], P, ids.shape[1])
+                if self.record_alignment:
+                    align_log.append(dict(sess.align_out, rows=[int(p) for p in batch_map], num_input_ids=P))
             else:
                 ids = sess.generate(torch.from_numpy(prompt), gen, max_length=eff_max,
                                     return_timestamps=return_timestamps)
@@ -296,29 +329,37 @@ class KWhisperForConditionalGeneration:
                 pass_ids.append(np.asarray(ids).copy())
             pad, eos = gen.pad_token_id, gen.eos_token_id
             for i, p in enumerate(batch_map):
-                seq = ids[i, P:]
-                if seq.size and seq[-1] == pad:
-                    n = int((seq == pad).sum())
-                    if pad == eos:
-                        n -= 1
-                    if n != 0:
-                        seq = seq[:-n]
-                if seq.size and seq[-1] == eos:
-                    seq = seq[:-1]
-                segs, off = _retrieve_segment(seq, ts_begin, int(seek_num[p]), float(time_offset[p]))
+                seq = _strip_pass_row(ids[i, P:], pad, eos)
+                segs, off = _retrieve_segment(seq, ts_begin, int(seek_num[p]), float(time_offset[p]),
+                                              token_ts=(pass_ts[i], ids[i], P) if token_ts else None)
                 seek[p] += off
                 segments[p] += segs
+            if token_ts:
+                last_ts = pass_ts
         self.stats = {"passes": passes, "row_passes": row_passes, "pass_log": pass_log}
         if self.record_pass_ids:
             self.stats["pass_ids"] = pass_ids
+        if token_ts and self.record_alignment:
+            self.stats["alignment"] = align_log
         if return_dict_in_generate and not return_timestamps:
-            return {"sequences": torch.from_numpy(last_ids).to(eng.device)}
+            res = {"sequences": torch.from_numpy(last_ids).to(eng.device)}
+            if token_ts:  # _stack_split_outputs: the single pass's timestamps, prompt positions included
+                res["token_timestamps"] = torch.from_numpy(last_ts).to(eng.device)
+            return res
         seqs = [np.concatenate([x["tokens"] for x in segs]) if segs else np.zeros(0, np.int64) for segs in segments]
         longest = max(len(x) for x in seqs) if seqs else 0
         out = np.full((B, longest), gen.pad_token_id, dtype=np.int64)
         for i, x in enumerate(seqs):
             out[i, : len(x)] = x
         res = torch.from_numpy(out).to(eng.device)
+        if token_ts:
+            # _pad_to_max_length (:188-229): each segment's slice of its pass's timestamps (no time offset), padded
+            # with the row's last value
+            tts = _pad_token_timestamps(segments, longest)
+            ret = {"sequences": res, "token_timestamps": torch.from_numpy(tts).to(eng.device)}
+            if return_segments or (return_dict_in_generate and return_timestamps):
+                ret["segments"] = segments
+            return ret
         if return_segments or (return_dict_in_generate and return_timestamps):
             return {"sequences": res, "segments": segments}
         return res
@@ -406,9 +447,65 @@ class KWhisperForConditionalGeneration:
         return np.broadcast_to(arr, (B, arr.shape[1])).copy()
 
 
+def _strip_pass_row(seq, pad, eos):
+    """A pass's generated tokens of one row without its padding and its EOS (generation_whisper.py:1063-1086)."""
+    if seq.size and seq[-1] == pad:
+        n = int((seq == pad).sum())
+        if pad == eos:
+            n -= 1
+        if n != 0:
+            seq = seq[:-n]
+    if seq.size and seq[-1] == eos:
+        seq = seq[:-1]
+    return seq
+
+
+def _pad_token_timestamps(segments, longest):
+    """The top-level ``token_timestamps`` (B, longest) float32 (_pad_to_max_length, :188-229): every segment's slice
+    of its pass's timestamps (no time offset), right-padded with the row's last value."""
+    tts = np.zeros((len(segments), longest), dtype=np.float32)
+    for i, segs in enumerate(segments):
+        x = np.concatenate([g["result"]["token_timestamps"][g["idxs"][0]: g["idxs"][1]] for g in segs]) \
+            if segs else np.zeros(0, np.float32)
+        tts[i, : len(x)] = x
+        tts[i, len(x):] = x[-1] if len(x) else 0.0
+    return tts
+
+
+def _pass_token_timestamps(frames, num_input_ids, length):
+    """One pass's ``_extract_token_timestamps`` result from the device's frame indices (B, T): float32 (B, length) =
+    zeros for the prompt, frame * 0.02 per step, the last time once more (:306-308, :336-339, :368-379)."""
+    B, T = frames.shape
+    out = np.zeros((B, length), dtype=np.float32)
+    if T > 0:
+        jt = frames.astype(np.int64) * 0.02
+        out[:, num_input_ids: num_input_ids + T] = jt
+        out[:, num_input_ids + T] = jt[:, -1]
+    return out
+
+
 def _retrieve_segment(seq, ts_begin, seek_num_frames, time_offset, input_stride=2, time_precision=0.02,
-                      time_precision_features=0.01):
-    """``_retrieve_segment`` (generation_whisper.py:1977-2074)."""
+                      time_precision_features=0.01, token_ts=None):
+    """``_retrieve_segment`` (generation_whisper.py:1977-2074).  ``token_ts`` = (the row's per-pass token timestamps,
+    its ids, the prompt length): segments then carry ``token_timestamps`` (their slice + time_offset), ``idxs`` and
+    ``result`` as the reference's do."""
+    segs, offset = _retrieve_segment_plain(seq, ts_begin, seek_num_frames, time_offset, input_stride, time_precision,
+                                           time_precision_features)
+    if token_ts is not None:
+        row_ts, row_ids, P = token_ts
+        result = {"sequences": row_ids, "token_timestamps": row_ts}
+        last = 0
+        for g in segs:
+            n = len(g["tokens"])
+            g["idxs"] = (P + last, P + last + n)
+            g["result"] = result
+            g["token_timestamps"] = row_ts[P + last: P + last + n] + np.float32(time_offset)
+            last += n
+    return segs, offset
+
+
+def _retrieve_segment_plain(seq, ts_begin, seek_num_frames, time_offset, input_stride=2, time_precision=0.02,
+                            time_precision_features=0.01):
     ts = seq >= ts_begin
     single_ending = ts[-2:].tolist() == [False, True]
     cons = np.where(ts[:-1] & ts[1:])[0] + 1

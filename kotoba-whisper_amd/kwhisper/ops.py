@@ -72,7 +72,7 @@ def _ws_bytes(kind: str, *dims) -> int:
     fn = {"dec_linear": "kw_dec_linear_workspace_bytes", "packed_weight": "kw_packed_weight_bytes",
           "self_attn": "kw_self_attn_workspace", "cross_attn": "kw_cross_attn_workspace",
           "greedy_step": "kw_greedy_step_workspace", "beam_logprobs": "kw_beam_logprobs_workspace",
-          "lm_greedy": "kw_dec_lm_greedy_workspace",
+          "lm_greedy": "kw_dec_lm_greedy_workspace", "dtw": "kw_dtw_workspace",
           "qkv_self": "kw_dec_qkv_self_workspace", "xq_cross": "kw_dec_xq_cross_workspace",
           "qkv_self_status": "kw_dec_qkv_self_status_offset", "xq_cross_status": "kw_dec_xq_cross_status_offset",
           "cross_attn_status": "kw_cross_attn_status_offset"}[kind]
@@ -649,3 +649,101 @@ class BeamStepPlan:
         else:
             L.check(_lib().kw_beam_logprobs(self._ra, _s()), "kw_beam_logprobs")
             L.check(_lib().kw_beam_select(self._rb, _s()), "kw_beam_select")
+
+
+# ---- token-level timestamps (csrc/token_ts.hip) ------------------------------------------------------------------
+def _i32s(vals):
+    return (ctypes.c_int32 * len(vals))(*[int(v) for v in vals])
+
+
+class AlignCapturePlan:
+    """Pre-built ``kw_align_capture`` call: one decode step's queries ``q`` [B][d] of one layer -> the 64-wide slices
+    of ``heads`` into ``log`` [A][B][t_log][64] at slots ``slots``, position read from the device ``cur_len``."""
+
+    def __init__(self, q, heads, slots, cur_len, begin_index, log):
+        _cuda(q, cur_len, log)
+        B, d = q.shape
+        if log.dim() != 4 or log.shape[1] != B or log.shape[3] != 64 or log.dtype != q.dtype or not log.is_contiguous():
+            raise ValueError("align capture log must be a contiguous [A][B][t_log][64] tensor of q's dtype")
+        if len(heads) != len(slots) or not 0 < len(heads) <= 32:
+            raise ValueError("align capture takes 1..32 heads of one layer, one log slot each")
+        if any(not 0 <= h < d // 64 for h in heads) or any(not 0 <= s < log.shape[0] for s in slots):
+            raise ValueError("align capture: head or log slot out of range")
+        self.q, self.heads, self.slots, self.cur_len, self.begin_index, self.log = q, [int(h) for h in heads], \
+            [int(s) for s in slots], cur_len, int(begin_index), log
+        self.tag = "align_capture"
+
+    def __call__(self):
+        if _BACKEND == "torch":
+            _kw().align_capture(self.q, self.heads, self.slots, self.cur_len, self.begin_index, self.log)
+            return
+        q, log = self.q, self.log
+        L.check(_lib().kw_align_capture(_dt(q), _p(q), q.shape[0], q.shape[1], _i32s(self.heads), _i32s(self.slots),
+                                        len(self.heads), log.shape[0], _p(self.cur_len), self.begin_index, _p(log),
+                                        log.shape[2], _s()), "kw_align_capture")
+
+
+def align_weights(qlog, k_cache, pairs, T, out, a0=0, layer_step=1):
+    """out [A][B][T][S] f32 = softmax over s of qlog[a0 + a][b][t] . k_cache[layer * layer_step][b][head][s] for the
+    ``pairs`` [(layer, head)] (<= 32 per call) and the first ``T`` logged steps."""
+    _cuda(qlog, k_cache, out)
+    flat = [int(v) for p in pairs for v in p]
+    if _BACKEND == "torch":
+        _kw().align_weights(qlog, int(a0), k_cache, int(layer_step), flat, int(T), out)
+        return out
+    A = len(pairs)
+    B, t_log = qlog.shape[1], qlog.shape[2]
+    H, S = k_cache.shape[2], k_cache.shape[3]
+    if (qlog.dim() != 4 or k_cache.dim() != 5 or not qlog.is_contiguous() or not k_cache.is_contiguous()
+            or k_cache.dtype != qlog.dtype or k_cache.shape[1] != B or a0 < 0 or a0 + A > qlog.shape[0]
+            or out.dtype != torch.float32 or not out.is_contiguous() or out.numel() < A * B * T * S):
+        raise ValueError("align_weights: qlog [A][B][t_log][64], k_cache [n][B][H][S][64], out f32 [A][B][T][S]")
+    q0 = ctypes.c_void_p(qlog.data_ptr() + a0 * B * t_log * 64 * qlog.element_size())
+    L.check(_lib().kw_align_weights(_dt(qlog), q0, t_log, _p(k_cache), layer_step * k_cache.stride(0),
+                                    (k_cache.shape[0] + layer_step - 1) // layer_step, _i32s(flat), A, B, H, S, int(T),
+                                    _p(out), _s()), "kw_align_weights")
+    return out
+
+
+def align_reduce(weights, A, B, T, S, frames, filter_width, out, a_total=None, first=True, last=True):
+    """weights [A][B][T][S] f32 -> the DTW matrix ``out`` [B][T][S] f32 (z-score over steps, median filter over the
+    row's first ``frames[b]`` frames, mean over the pairs, negated); ``first`` / ``last`` chain chunks of pairs."""
+    _cuda(weights, frames, out)
+    a_total = A if a_total is None else a_total
+    if _BACKEND == "torch":
+        _kw().align_reduce(weights, A, B, T, S, frames, int(filter_width), out, int(a_total), int(first), int(last))
+        return out
+    if (weights.dtype != torch.float32 or out.dtype != torch.float32 or not weights.is_contiguous()
+            or not out.is_contiguous() or weights.numel() < A * B * T * S or out.numel() < B * T * S
+            or (frames is not None and (frames.dtype != torch.int32 or frames.numel() < B))):
+        raise ValueError("align_reduce: weights [A][B][T][S] f32, out [B][T][S] f32, frames int32 [B]")
+    L.check(_lib().kw_align_reduce(_p(weights), A, B, T, S, _p(frames), int(filter_width), _p(out), int(a_total),
+                                   int(first), int(last), _s()), "kw_align_reduce")
+    return out
+
+
+def dtw_workspace_bytes(B, T, S) -> int:
+    return _ws_bytes("dtw", B, T, S)
+
+
+def dtw(matrix, frames=None, out=None, workspace=None):
+    """matrix [B][T][S] f32 (row b: its first ``frames[b]`` columns) -> int32 [B][T]: the frame index at which the
+    DTW path first reaches each step."""
+    _cuda(matrix, frames, out, workspace)
+    if matrix.dim() != 3 or matrix.dtype != torch.float32 or not matrix.is_contiguous():
+        raise ValueError("dtw: matrix must be a contiguous [B][T][S] float32 tensor")
+    B, T, S = matrix.shape
+    if frames is not None and (frames.dtype != torch.int32 or frames.numel() < B):
+        raise ValueError("dtw: frames must be int32 [B]")
+    if out is None:
+        out = torch.empty((B, T), device=matrix.device, dtype=torch.int32)
+    if workspace is None:
+        workspace = torch.empty((dtw_workspace_bytes(B, T, S),), device=matrix.device, dtype=torch.uint8)
+    if _BACKEND == "torch":
+        _kw().dtw(matrix, frames, out, workspace)
+        return out
+    if out.dtype != torch.int32 or not out.is_contiguous() or out.numel() < B * T:
+        raise ValueError("dtw: out must be a contiguous int32 [B][T] tensor")
+    L.check(_lib().kw_dtw(_p(matrix), B, T, S, _p(frames), _p(out), _p(workspace),
+                          workspace.numel() * workspace.element_size(), _s()), "kw_dtw")
+    return out

@@ -682,6 +682,130 @@ def pipeline_fixtures(tags=("tiny", "tiny_longform", "kotoba_v2")):
         suffix = "" if len(PIPE_CASES[tag]) > 6 else "_fp32"  # (the bf16 case's tag says its dtype)
         np.savez_compressed(os.path.join(GOLD, f"pipeline_{tag}{suffix}.npz"), **out)
 
+# ---- token-level timestamps (return_token_timestamps) ----------------------------------------------------------
+TOKEN_TS_HEADS = [[2, 2], [3, 0], [3, 2], [3, 3], [3, 4], [3, 5]]
+TOKEN_TS_CLIPS = [("dummy", 0), ("tone", 1), ("dummy", 2), ("tone", 3)]
+TOKEN_TS_MASK = {1: 2000, 3: 1200}  # row -> valid feature frames (the others: all 3000)
+TOKEN_TS_MODES = {"ts": dict(return_timestamps=True, max_length=64), "nots": dict(return_timestamps=False, max_length=48)}
+TOKEN_TS_TSTRIDE, TOKEN_TS_SSTRIDE = 9, 29  # the stored sample of the raw alignment weights
+TOKEN_TS_NOISE, TOKEN_TS_DRAWS = 32.0, 3    # stability: relative noise in units of eps_ref, seeded draws
+
+
+class _TokenTsRecorder:
+    """Wraps one HF model's ``_postprocess_outputs`` / ``_extract_token_timestamps`` and keeps, per seek pass, what
+    went in (rows, prompt length, frame counts, the alignment heads' raw weights) and what came out."""
+
+    def __init__(self, m):
+        self.m, self.passes, self._ctx = m, [], None
+        self._post, self._ext = m._postprocess_outputs, m._extract_token_timestamps
+        m._postprocess_outputs, m._extract_token_timestamps = self.post, self.extract
+
+    def close(self):
+        del self.m._postprocess_outputs, self.m._extract_token_timestamps
+
+    def post(self, **kw):
+        self._ctx = [int(i) for i in kw["batch_idx_map"]]
+        return self._post(**kw)
+
+    def weights(self, outs, heads, num_input_ids):
+        L = self.m.config.decoder_layers
+        cross = [torch.cat([x[i] for x in outs.cross_attentions], dim=2) for i in range(L)]
+        w = torch.stack([cross[l][:, h] for l, h in heads]).permute([1, 0, 2, 3])
+        return w[:, :, num_input_ids:, :]
+
+    def extract(self, outs, heads, time_precision=0.02, num_frames=None, num_input_ids=None):
+        ts = self._ext(outs, heads, time_precision=time_precision, num_frames=num_frames, num_input_ids=num_input_ids)
+        nf = None if num_frames is None else np.asarray(num_frames).astype(np.int64).reshape(-1)
+        self.passes.append(dict(rows=self._ctx, P=int(num_input_ids), num_frames=nf, ts=ts.numpy().copy(), outs=outs,
+                                heads=heads, weights=self.weights(outs, heads, num_input_ids).numpy().copy(),
+                                sequences=outs.sequences.numpy().copy()))
+        return ts
+
+    def perturbed(self, p, rel, seed):
+        """HF's timestamps of pass ``p`` with every cross-attention weight multiplied by 1 + rel * N(0, 1)."""
+        g = torch.Generator().manual_seed(seed)
+        outs = p["outs"]
+        old = outs.cross_attentions
+        outs.cross_attentions = tuple(tuple(x * (1 + rel * torch.randn(x.shape, generator=g, dtype=x.dtype)) for x in st)
+                                      for st in old)
+        try:
+            nf = None if p["num_frames"] is None else torch.from_numpy(p["num_frames"])
+            return self._ext(outs, p["heads"], num_frames=nf, num_input_ids=p["P"]).numpy()
+        finally:
+            outs.cross_attentions = old
+
+
+def _token_ts_run(m, feats, mask, heads, **kw):
+    gconf, _ = hf_gen_config(TINY)
+    gconf.alignment_heads = heads
+    m.generation_config = gconf
+    rec = _TokenTsRecorder(m)
+    try:
+        with torch.no_grad():
+            res = m.generate(feats, attention_mask=mask, language="ja", task="transcribe", return_token_timestamps=True,
+                             return_segments=True, **kw)
+    finally:
+        rec.close()
+    return res, rec
+
+
+def token_ts_fixtures():
+    t0 = time.time()
+    feats = features(TINY.num_mel_bins, TOKEN_TS_CLIPS)
+    mask = torch.ones((feats.shape[0], feats.shape[-1]), dtype=torch.long)
+    for r, n in TOKEN_TS_MASK.items():
+        mask[r, n:] = 0
+    out = {"cases": np.array([f"{k}:{s}" for k, s in TOKEN_TS_CLIPS]), "alignment_heads": np.array(TOKEN_TS_HEADS),
+           "attention_frames": mask.sum(-1).numpy(), "tstride": TOKEN_TS_TSTRIDE, "sstride": TOKEN_TS_SSTRIDE}
+    m32, m64 = hf_model(TINY), hf_model(TINY).double()
+    n_stable = n_all = 0
+    for name, kw in TOKEN_TS_MODES.items():
+        res, rec = _token_ts_run(m32, feats, mask, TOKEN_TS_HEADS, **kw)
+        res64, rec64 = _token_ts_run(m64, feats.double(), mask, TOKEN_TS_HEADS, **kw)
+        assert torch.equal(res["sequences"], res64["sequences"]) and len(rec.passes) == len(rec64.passes)
+        out[f"{name}_kw"] = json.dumps(kw)
+        out[f"{name}_sequences"] = res["sequences"].numpy().astype(np.int64)
+        out[f"{name}_token_timestamps"] = res["token_timestamps"].numpy().astype(np.float32)
+        out[f"{name}_passes"] = len(rec.passes)
+        for b, row in enumerate(res["segments"]):
+            out[f"{name}_seg_len_{b}"] = np.array([len(g["tokens"]) for g in row], dtype=np.int64)
+            out[f"{name}_seg_tts_{b}"] = (np.concatenate([g["token_timestamps"].numpy() for g in row]).astype(np.float32)
+                                         if row else np.zeros(0, np.float32))
+        for i, (p, p64) in enumerate(zip(rec.passes, rec64.passes)):
+            assert np.array_equal(p["sequences"], p64["sequences"]) and p["rows"] == p64["rows"]
+            w, w64 = p["weights"], p64["weights"]  # [rows][A][T][S]
+            sm = (slice(None), slice(None), slice(None, None, TOKEN_TS_TSTRIDE), slice(None, None, TOKEN_TS_SSTRIDE))
+            ws, ws64 = w[sm], w64[sm]
+            eps = float((np.abs(ws.astype(np.float64) - ws64).max(-1) / ws64.max(-1)).max()) if ws.size else 0.0
+            out[f"{name}_p{i}_rows"] = np.array(p["rows"])
+            out[f"{name}_p{i}_P"] = p["P"]
+            out[f"{name}_p{i}_num_frames"] = p["num_frames"]
+            out[f"{name}_p{i}_sequences"] = p["sequences"].astype(np.int64)
+            out[f"{name}_p{i}_ts"] = p["ts"].astype(np.float32)
+            out[f"{name}_p{i}_shape"] = np.array([[w.shape[2], n // 2] for n in p["num_frames"]])  # (steps, frames)
+            out[f"{name}_p{i}_w32"] = ws.astype(np.float32)
+            out[f"{name}_p{i}_w64"] = ws64.astype(np.float64)
+            out[f"{name}_p{i}_eps_ref"] = eps
+            stable = np.ones(len(p["rows"]), dtype=bool)
+            for d in range(TOKEN_TS_DRAWS):
+                stable &= (rec.perturbed(p, TOKEN_TS_NOISE * eps, 1000 * i + d) == p["ts"]).all(-1)
+            out[f"{name}_p{i}_stable"] = stable
+            n_stable, n_all = n_stable + int(stable.sum()), n_all + stable.size
+            print(f"  token_ts {name} pass {i}: rows {p['rows']} steps {w.shape[2]} frames "
+                  f"{[int(n) // 2 for n in p['num_frames']]} eps_ref {eps:.2e} stable {stable.tolist()}")
+    assert 4 * n_stable >= 3 * n_all, f"only {n_stable} of {n_all} (pass, row) cases are stable: pick other clips"
+    # the tiny full-weights case that pins the numpy restatement: B = 1, 2 heads, 11 steps (12 new tokens)
+    res, rec = _token_ts_run(m32, feats[:1], mask[:1] * 0 + (torch.arange(mask.shape[1]) < 2000), TOKEN_TS_HEADS[:2],
+                             return_timestamps=False, max_new_tokens=12)
+    (p,) = rec.passes
+    assert p["weights"].shape[2] <= 12
+    out["pin_weights"] = p["weights"][0].astype(np.float32)  # [2][steps][1500]
+    out["pin_num_frames"] = int(p["num_frames"][0])
+    out["pin_P"] = p["P"]
+    out["pin_ts"] = p["ts"][0].astype(np.float32)
+    np.savez_compressed(os.path.join(GOLD, "token_ts_tiny.npz"), **out)
+    print(f"token_ts fixtures done: {n_stable}/{n_all} stable ({time.time() - t0:.1f}s)")
+
 
 def main():
     ap = argparse.ArgumentParser()
@@ -713,6 +837,8 @@ def main():
     ]
     if a.only in (None, "beam"):
         beam_fixtures()
+    if a.only in (None, "token_ts"):
+        token_ts_fixtures()
     if a.only in (None, "longform"):
         longform_fixtures()
     if a.only in (None, "tiny"):
