@@ -329,6 +329,68 @@ int kw_dec_lm_greedy(const kw_dec_linear_args* lm, const kw_sampler_args* g, kw_
 size_t kw_dec_lm_greedy_workspace(int64_t B, int64_t V);
 int kw_dec_lm_greedy_supported(int64_t B, int64_t V, int64_t d);
 
+/* ---- sampling step with running log-probabilities (additive, ABI 112 unchanged) -------------------------
+ * One decode step's token choice for all rows, for Whisper's temperature fallback (TF models/whisper/
+ * generation_whisper.py:970-1116; sampling as TF generation/utils.py _sample: processors, temperature warp, softmax,
+ * multinomial).  The processors, the finished-row handling (pad), the stopping rules, the *cur_len advance and
+ * *n_unfinished are kw_greedy_step's, so the step replays from the same hipGraph loop; both return_timestamps modes.
+ * Every row is split over several workgroups whose partials the row's last arriver merges (as kw_greedy_step with a
+ * workspace), so workspace is REQUIRED: >= kw_sample_step_workspace(B) bytes, zero-filled once (launches leave it zeroed).
+ *
+ * Token.  s(v) = the processed scores (SuppressTokens, SuppressTokensAtBegin, WhisperTimeStamp with its probability-
+ * mass rule evaluated on the un-warped scores).  *inv_temperature == 0: argmax_v s(v), first index on ties -- exactly
+ * kw_greedy_step's token.  Otherwise argmax_v( s(v) * inv_temperature + g(v) ) over the v with s(v) > -inf (first index
+ * on ties), g = Gumbel noise: in distribution softmax(s / T) followed by a multinomial draw.
+ *
+ * Noise.  Counter-based Philox4x32-10 (multipliers 0xD2511F53 on word 0, 0xCD9E8D57 on word 2; key increments
+ * 0x9E3779B9, 0xBB67AE85; ten rounds), generated in the kernel:
+ *   counter = (v >> 2, L, row, *attempt)   L = the position written (*cur_len at entry), row = the row's index b
+ *   key     = (low, high) 32-bit halves of *seed
+ *   x       = output word v & 3
+ * so the noise of (seed, attempt, row, L, v) does not depend on B, on the split or on the grid.  The uniform takes the
+ * TOP 20 BITS of x: u = ((x >> 12) + 0.5) * 2^-20, in [2^-21, 1 - 2^-21], and g = -logf(-logf(u)) (f32), finite for
+ * every x: g in [-2.679, 14.557].  (20 bits: the draw stays recoverable from the stored f32 g, see noise_out.)
+ *
+ * Running statistics, for the rows not finished before this step (first EOS counted, pad positions after it not):
+ *   sum_logprob[b] += s(tok) - logsumexp_v s(v)   and   n_tokens[b] += 1     (f32, in step order)
+ * over the fully processed scores -- when the mass rule bans text the normaliser runs over the timestamps only -- and
+ * without the temperature (TF generation_whisper.py:1958-1974: scores * rescale_temperature); sum / n is
+ * _retrieve_avg_logprobs' value.  The caller zeroes both before the first step of a decode.
+ *
+ * active (optional, [B] uint8): a row with 0 is finished from the first step -- it emits pad, is not counted in
+ * *n_unfinished and accumulates nothing (a fallback attempt re-decodes only the rows that need it).
+ * noise_out (optional, [B][V] f32): receives g(v) for every v (0 when *inv_temperature == 0); validation only.
+ * inv_temperature, seed and attempt are DEVICE pointers read by the launch: one captured graph serves a schedule. */
+typedef struct {
+  const float* logits;        /* [B][V] f32 raw logits */
+  int64_t B, V;
+  const uint8_t* suppress_mask;
+  const int32_t* begin_suppress;
+  int32_t n_begin_suppress;
+  int32_t return_timestamps;
+  int32_t ts_begin, no_ts_id, eos_id, pad_id;
+  int32_t max_initial_ts;     /* -1 = None */
+  int64_t* ids;               /* [B][ids_stride] */
+  int64_t ids_stride;
+  int32_t* cur_len;
+  int32_t max_length, begin_index;
+  int32_t* unfinished;        /* [B] */
+  int32_t* counter;           /* [1] scratch, zero before first use */
+  int32_t* n_unfinished;      /* [1] */
+  const float* inv_temperature; /* [1] 1 / T, or 0 for the argmax */
+  const uint64_t* seed;       /* [1] */
+  const uint32_t* attempt;    /* [1] */
+  float* sum_logprob;         /* [B] in/out */
+  int32_t* n_tokens;          /* [B] in/out */
+  const uint8_t* active;      /* [B] or NULL */
+  float* noise_out;           /* [B][V] or NULL */
+  void* workspace;
+  size_t ws_bytes;
+} kw_sample_args;
+
+int kw_sample_step(const kw_sample_args* args, kw_stream_t stream);
+size_t kw_sample_step_workspace(int64_t B);
+
 /* ---- beam search step (a10: TF/generation/utils.py:3208-3527), num_return_sequences = 1 ----------
  * Running rows are R = B * num_beams, item-major (row = b * num_beams + beam).  One step is
  * kw_beam_logprobs then kw_beam_select; both read the device cur_len and do nothing once *done != 0,

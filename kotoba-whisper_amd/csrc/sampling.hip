@@ -412,7 +412,256 @@ __global__ __launch_bounds__(SPLIT_T) void greedy_step_split_ts_kernel(kw_sample
   }
 }
 
+// ---- sampling step with running log-probabilities (kw_sample_step; include/kwhisper.h has the contract) ----
+// greedy_step_split_ts_kernel's split, publish and last-arriver merge, in both timestamp modes, with two additions:
+// every slice also keeps the best PERTURBED score s * inv_T + g of its text and of its timestamp tokens (the mass
+// rule needs the whole row before text may be chosen, so the merge decides between them), and the row's merge adds
+// the chosen token's log-probability under the processed, un-warped scores to the row's running sum.
+
+// Philox4x32-10 (Salmon et al., SC'11): word `w` of the block of counter c, key k
+__device__ __forceinline__ uint32_t philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
+                                                  uint32_t k1, int w) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const uint32_t hi0 = __umulhi(0xD2511F53u, c0), lo0 = 0xD2511F53u * c0;
+    const uint32_t hi1 = __umulhi(0xCD9E8D57u, c2), lo1 = 0xCD9E8D57u * c2;
+    c0 = hi1 ^ c1 ^ k0;
+    c1 = lo1;
+    c2 = hi0 ^ c3 ^ k1;
+    c3 = lo0;
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return w == 0 ? c0 : w == 1 ? c1 : w == 2 ? c2 : c3;
+}
+
+// the top 20 bits of a draw -> u in [2^-21, 1 - 2^-21] -> Gumbel noise in [-2.679, 14.557] (finite for every draw)
+__device__ __forceinline__ float gumbel_noise(uint32_t x) {
+  const float u = ((float)(x >> 12) + 0.5f) * 0x1p-20f;
+  return -logf(-logf(u));
+}
+
+struct SampleRng {
+  uint32_t k0, k1, L, row, attempt;
+  float inv_t;
+  bool on;
+  float* out;  // the row's noise_out or NULL
+  __device__ __forceinline__ float perturb(int v, float s) const {
+    float g = 0.f;
+    if (on) g = gumbel_noise(philox4x32_10((uint32_t)v >> 2, L, row, attempt, k0, k1, v & 3));
+    if (out) out[v] = g;
+    return on ? s * inv_t + g : s;
+  }
+};
+
+__global__ __launch_bounds__(SPLIT_T) void sample_step_kernel(kw_sample_args a) {
+  __shared__ float shf[SPLIT_T / 64];
+  __shared__ int shi[SPLIT_T / 64];
+  __shared__ RowState st_sh;
+  const int b = blockIdx.x, sl = blockIdx.y;
+  const int tid = threadIdx.x;
+  const int L = *a.cur_len;
+  const int64_t* ids = a.ids + (int64_t)b * a.ids_stride;
+  const float* x = a.logits + (int64_t)b * a.V;
+  const int V = (int)a.V;
+  const int per = (V + NSPLIT - 1) / NSPLIT;
+  const int v0 = sl * per, v1 = min(V, v0 + per);
+  float xv[SUNR];
+  bool mk[SUNR];
+#pragma unroll
+  for (int u = 0; u < SUNR; ++u) {  // the slice's logits and mask bytes in flight while the history is scanned
+    const int v = v0 + tid + u * SPLIT_T, vc = min(v, v1 - 1);  // unconditional (clamped) loads: no branches
+    const float xr = x[vc];                                           // and phis between them
+    const uint8_t mr = a.suppress_mask[vc];
+    xv[u] = v < v1 ? xr : -INFINITY;
+    mk[u] = v < v1 ? mr != 0 : true;
+  }
+  SampleRng rng;
+  {
+    const uint64_t seed = *a.seed;
+    rng.k0 = (uint32_t)seed, rng.k1 = (uint32_t)(seed >> 32);
+    rng.L = (uint32_t)L, rng.row = (uint32_t)b, rng.attempt = *a.attempt;
+    rng.inv_t = *a.inv_temperature;
+    rng.on = rng.inv_t != 0.f;
+    rng.out = a.noise_out ? a.noise_out + (int64_t)b * a.V : nullptr;
+  }
+  // ---- row state from the id history (as greedy_step_split_ts_kernel); an inactive row is finished ----
+  int fin = a.active ? a.active[b] == 0 : 0, lsp = -1;
+  for (int p = a.begin_index + tid; p < L; p += SPLIT_T) {
+    const int64_t t = ids[p];
+    fin |= t == a.eos_id;
+    if (t >= a.ts_begin) lsp = max(lsp, p);
+  }
+  fin = __syncthreads_or(fin);
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) lsp = max(lsp, __shfl_xor(lsp, o, 64));
+  if ((tid & 63) == 0) shi[tid >> 6] = lsp;
+  __syncthreads();
+  if (tid == 0) {
+    int lp = shi[0];
+    for (int i = 1; i < SPLIT_T / 64; ++i) lp = max(lp, shi[i]);
+    RowState st;
+    st.L = L; st.begin = a.begin_index; st.ts_begin = a.ts_begin; st.no_ts = a.no_ts_id; st.eos = a.eos_id;
+    st.rt = a.return_timestamps != 0; st.max_init = a.max_initial_ts; st.ban_text = 0;
+    const int n = L - a.begin_index;
+    st.first_step = (L == a.begin_index);
+    st.last_ts = n >= 1 && ids[L - 1] >= a.ts_begin;
+    st.pen_ts = n < 2 || ids[L - 2] >= a.ts_begin;
+    st.has_stamp = lp >= 0;
+    st.stamp_lo = st.has_stamp ? ((st.last_ts && !st.pen_ts) ? (int)ids[lp] : (int)ids[lp] + 1) : 0;
+    st_sh = st;
+  }
+  __syncthreads();
+  const RowState st = st_sh;
+  // ---- processed scores of the slice (held in registers): plain and perturbed maxima of both classes ----
+  float sv[SUNR];
+  float mt = -INFINITY, ms = -INFINITY, pt = -INFINITY, ps = -INFINITY;
+  int jt = 0x7fffffff, js = 0x7fffffff;
+#pragma unroll
+  for (int u = 0; u < SUNR; ++u) {
+    const int v = v0 + tid + u * SPLIT_T;
+    sv[u] = v < v1 ? process_m(st, mk[u], a.begin_suppress, a.n_begin_suppress, v, xv[u]) : -INFINITY;
+    if (v < v1) {
+      const float p = rng.perturb(v, sv[u]);
+      if (v < st.ts_begin) {
+        mt = fmaxf(mt, sv[u]);
+        if (sv[u] > -INFINITY && (p > pt || (p == pt && v < jt))) { pt = p; jt = v; }
+      } else {
+        ms = fmaxf(ms, sv[u]);
+        if (sv[u] > -INFINITY && (p > ps || (p == ps && v < js))) { ps = p; js = v; }
+      }
+    }
+  }
+  for (int vb = v0 + SPLIT_T * SUNR; vb < v1; vb += SPLIT_T) {  // V > NSPLIT * 8192 only
+    const int v = vb + tid;
+    if (v < v1) {
+      const float s = process(st, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, v, x[v]);
+      const float p = rng.perturb(v, s);
+      if (v < st.ts_begin) {
+        mt = fmaxf(mt, s);
+        if (s > -INFINITY && (p > pt || (p == pt && v < jt))) { pt = p; jt = v; }
+      } else {
+        ms = fmaxf(ms, s);
+        if (s > -INFINITY && (p > ps || (p == ps && v < js))) { ps = p; js = v; }
+      }
+    }
+  }
+  blk_argmax(pt, jt, shf, shi);
+  blk_argmax(ps, js, shf, shi);
+  mt = blk_max(mt, shf);
+  ms = blk_max(ms, shf);
+  const float mall = fmaxf(mt, ms);
+  float sa = 0.f, sts = 0.f;
+  if (mall > -INFINITY) {
+#pragma unroll
+    for (int u = 0; u < SUNR; ++u) {
+      const int v = v0 + tid + u * SPLIT_T;
+      if (v < v1 && sv[u] > -INFINITY) {
+        sa += expf(sv[u] - mall);
+        if (v >= st.ts_begin) sts += expf(sv[u] - ms);
+      }
+    }
+    for (int vb = v0 + SPLIT_T * SUNR; vb < v1; vb += SPLIT_T) {
+      const int v = vb + tid;
+      if (v < v1) {
+        const float s = process(st, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, v, x[v]);
+        if (s > -INFINITY) {
+          sa += expf(s - mall);
+          if (v >= st.ts_begin) sts += expf(s - ms);
+        }
+      }
+    }
+  }
+  sa = blk_sum(sa, shf);
+  sts = blk_sum(sts, shf);
+  if (tid != 0) return;
+  float* part = reinterpret_cast<float*>(a.workspace) + ((int64_t)b * NSPLIT + sl) * PART;
+  int* rcnt = reinterpret_cast<int*>(a.workspace) + (int64_t)a.B * NSPLIT * PART + b;
+  const float vals[8] = {mt, ms, sa, sts, pt, __int_as_float(jt), ps, __int_as_float(js)};
+#pragma unroll
+  for (int i = 0; i < 8; ++i) __hip_atomic_store(part + i, vals[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  const int prev = __hip_atomic_fetch_add(rcnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (prev != NSPLIT - 1) return;
+  __hip_atomic_store(rcnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const float* row = reinterpret_cast<const float*>(a.workspace) + (int64_t)b * NSPLIT * PART;
+  float P[NSPLIT][8];
+#pragma unroll
+  for (int q = 0; q < NSPLIT; ++q)  // every partial load in flight before the merge
+#pragma unroll
+    for (int i = 0; i < 8; ++i) P[q][i] = __hip_atomic_load(row + PART * q + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  float bt = -INFINITY, bs = -INFINITY, bpt = -INFINITY, bps = -INFINITY;
+  int kt = 0x7fffffff, ks = 0x7fffffff;
+  for (int q = 0; q < NSPLIT; ++q) {  // slice order = index order
+    const int qt = __float_as_int(P[q][5]), qs = __float_as_int(P[q][7]);
+    bt = fmaxf(bt, P[q][0]);
+    bs = fmaxf(bs, P[q][1]);
+    if (P[q][4] > bpt || (P[q][4] == bpt && qt < kt)) { bpt = P[q][4]; kt = qt; }
+    if (P[q][6] > bps || (P[q][6] == bps && qs < ks)) { bps = P[q][6]; ks = qs; }
+  }
+  const float M = fmaxf(bt, bs), Mts = bs;
+  float S = 0.f, Sts = 0.f;
+  for (int q = 0; q < NSPLIT; ++q) {
+    const float qm = fmaxf(P[q][0], P[q][1]);
+    if (qm > -INFINITY) S += P[q][2] * expf(qm - M);
+    if (P[q][1] > -INFINITY) Sts += P[q][3] * expf(P[q][1] - Mts);
+  }
+  int ban = 0;
+  if (st.rt && M > -INFINITY) {  // the mass rule, on the un-warped scores (as greedy_step_split_ts_kernel)
+    const float lse = logf(S);
+    const float lp_text_max = (bt - M) - lse;
+    const float lp_ts_max = (Mts - M) - lse;
+    const float ts_lse = lp_ts_max > -INFINITY ? lp_ts_max + logf(Sts) : -INFINITY;
+    ban = ts_lse > lp_text_max;
+  }
+  int ii;
+  if (ban) ii = ks;
+  else ii = (bps > bpt) ? ks : kt;  // a tie keeps the text token (the lower index)
+  const bool none = ii == 0x7fffffff;
+  if (none) ii = 0;
+  const int64_t tok = fin ? (int64_t)a.pad_id : (int64_t)ii;
+  a.ids[(int64_t)b * a.ids_stride + L] = tok;
+  if (!fin) {
+    // log-probability of the token under the processed scores: with text banned they are the timestamps alone
+    RowState sb = st;
+    sb.ban_text = ban;
+    const float s_tok = none ? -INFINITY : process(sb, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, ii, x[ii]);
+    const float lp = ban ? (s_tok - Mts) - logf(Sts) : (s_tok - M) - logf(S);
+    a.sum_logprob[b] += lp;
+    a.n_tokens[b] += 1;
+  }
+  const int done = fin || tok == a.eos_id || (L + 1) >= a.max_length;
+  a.unfinished[b] = done ? 0 : 1;
+  __threadfence();
+  const int prev2 = atomicAdd(a.counter, 1);
+  if (prev2 == (int)a.B - 1) {
+    __threadfence();
+    int n = 0;
+    for (int i = 0; i < (int)a.B; ++i) n += __hip_atomic_load(a.unfinished + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    *a.n_unfinished = n;
+    *a.counter = 0;
+    *a.cur_len = L + 1;
+    __threadfence();
+  }
+}
+
 }  // namespace
+
+extern "C" size_t kw_sample_step_workspace(int64_t B) {
+  return (size_t)B * NSPLIT * PART * sizeof(float) + (size_t)B * sizeof(int);
+}
+
+extern "C" int kw_sample_step(const kw_sample_args* a, kw_stream_t stream) {
+  if (!a || !a->logits || !a->suppress_mask || !a->ids || !a->cur_len || !a->unfinished || !a->counter || !a->n_unfinished ||
+      !a->inv_temperature || !a->seed || !a->attempt || !a->sum_logprob || !a->n_tokens || a->B <= 0 || a->V <= 0 ||
+      a->V > 0x7fffffff || (a->n_begin_suppress > 0 && !a->begin_suppress))
+    return kw_set_error_msg(KW_EINVAL, "kw_sample_step: invalid arguments");
+  if (!a->workspace || a->ws_bytes < kw_sample_step_workspace(a->B))
+    return kw_set_error_msg(KW_EINVAL, "kw_sample_step: workspace missing or smaller than kw_sample_step_workspace(B)");
+  hipLaunchKernelGGL(sample_step_kernel, dim3((unsigned)a->B, NSPLIT), dim3(SPLIT_T), 0, (hipStream_t)stream, *a);
+  KW_CHECK_LAUNCH();
+  return KW_OK;
+}
 
 extern "C" size_t kw_greedy_step_workspace(int64_t B) {
   return (size_t)B * NSPLIT * PART * sizeof(float) + (size_t)B * sizeof(int);

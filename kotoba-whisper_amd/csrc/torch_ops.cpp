@@ -321,6 +321,63 @@ void greedy_step(Tensor& logits, const Tensor& suppress_mask, const optional<Ten
   check(kw_greedy_step(&a, stream_of(logits)), w);
 }
 
+// ---- sampling step with running log-probabilities -------------------------------------------------------
+// cfg = [return_timestamps, ts_begin, no_ts_id, eos_id, pad_id, max_initial_ts, max_length, begin_index];
+// inv_temperature f32 [1], seed int64 [1] (its 64 bits are the key), attempt int32 [1]
+void sample_step(const Tensor& logits, const Tensor& suppress_mask, const optional<Tensor>& begin_suppress, Tensor& ids,
+                 Tensor& cur_len, Tensor& unfinished, Tensor& counter, Tensor& n_unfinished, const Tensor& inv_temperature,
+                 const Tensor& seed, const Tensor& attempt, Tensor& sum_logprob, Tensor& n_tokens,
+                 const optional<Tensor>& active, optional<Tensor> noise_out, Tensor& workspace, std::vector<int64_t> cfg) {
+  const char* w = "kw_sample_step";
+  dev(logits, w), dev(suppress_mask, w), dev(begin_suppress, w), dev(ids, w), dev(cur_len, w), dev(unfinished, w);
+  dev(counter, w), dev(n_unfinished, w), dev(inv_temperature, w), dev(seed, w), dev(attempt, w), dev(sum_logprob, w);
+  dev(n_tokens, w), dev(active, w), dev(noise_out, w), dev(workspace, w);
+  TORCH_CHECK_VALUE(cfg.size() == 8, "kw_sample_step: cfg must hold 8 integers");
+  TORCH_CHECK_VALUE(logits.dim() == 2 && logits.is_contiguous() && logits.scalar_type() == at::kFloat,
+                    "kw_sample_step: logits must be a contiguous (B, V) float32 tensor");
+  const int64_t B = logits.size(0), V = logits.size(1);
+  TORCH_CHECK_VALUE(inv_temperature.scalar_type() == at::kFloat && seed.scalar_type() == at::kLong &&
+                        attempt.scalar_type() == at::kInt && sum_logprob.scalar_type() == at::kFloat &&
+                        n_tokens.scalar_type() == at::kInt && sum_logprob.numel() >= B && n_tokens.numel() >= B,
+                    "kw_sample_step: inv_temperature f32 [1], seed int64 [1], attempt int32 [1], sum_logprob f32 [B], "
+                    "n_tokens int32 [B]");
+  TORCH_CHECK_VALUE(!active.has_value() || (active->scalar_type() == at::kByte && active->numel() >= B),
+                    "kw_sample_step: active must be uint8 [B]");
+  TORCH_CHECK_VALUE(!noise_out.has_value() || (noise_out->scalar_type() == at::kFloat && noise_out->is_contiguous() &&
+                                               noise_out->numel() >= B * V),
+                    "kw_sample_step: noise_out must be a contiguous float32 [B][V] tensor");
+  TORCH_CHECK_VALUE(suppress_mask.numel() >= V && unfinished.numel() >= B && ids.size(0) >= B && ids.stride(1) == 1 &&
+                        ids.size(1) > cfg[6] - 1,
+                    "kw_sample_step: suppress_mask [V], unfinished [B], ids [B][>= max_length]");
+  kw_sample_args a{};
+  a.logits = ptr<const float>(logits);
+  a.B = B, a.V = V;
+  a.suppress_mask = ptr<const uint8_t>(suppress_mask);
+  a.begin_suppress = optr<const int32_t>(begin_suppress);
+  a.n_begin_suppress = begin_suppress.has_value() ? (int32_t)begin_suppress->numel() : 0;
+  a.return_timestamps = (int32_t)cfg[0];
+  a.ts_begin = (int32_t)cfg[1], a.no_ts_id = (int32_t)cfg[2], a.eos_id = (int32_t)cfg[3], a.pad_id = (int32_t)cfg[4];
+  a.max_initial_ts = (int32_t)cfg[5];
+  a.ids = ptr<int64_t>(ids);
+  a.ids_stride = ids.stride(0);
+  a.cur_len = ptr<int32_t>(cur_len);
+  a.max_length = (int32_t)cfg[6], a.begin_index = (int32_t)cfg[7];
+  a.unfinished = ptr<int32_t>(unfinished);
+  a.counter = ptr<int32_t>(counter);
+  a.n_unfinished = ptr<int32_t>(n_unfinished);
+  a.inv_temperature = ptr<const float>(inv_temperature);
+  a.seed = ptr<const uint64_t>(seed);
+  a.attempt = ptr<const uint32_t>(attempt);
+  a.sum_logprob = ptr<float>(sum_logprob);
+  a.n_tokens = ptr<int32_t>(n_tokens);
+  a.active = optr<const uint8_t>(active);
+  a.noise_out = optr<float>(noise_out);
+  a.workspace = ptr(workspace);
+  a.ws_bytes = (size_t)workspace.numel() * workspace.element_size();
+  c10::DeviceGuard g(logits.device());
+  check(kw_sample_step(&a, stream_of(logits)), w);
+}
+
 // ---- LM head + greedy step in one launch (no timestamps) ------------------------------------------------
 // lm_geo = [x_offset, ldx, M, N, K]; cfg = [eos_id, pad_id, max_length, begin_index]
 void dec_lm_greedy(const Tensor& x, const Tensor& W, const optional<Tensor>& bias, const Tensor& ln_colsum,
@@ -512,6 +569,7 @@ int64_t workspace_bytes(std::string kind, std::vector<int64_t> d) {
   if (kind == "self_attn") return (int64_t)kw_self_attn_workspace(n(0), n(1), n(2));
   if (kind == "cross_attn") return (int64_t)kw_cross_attn_workspace(n(0), n(1), n(2), n(3), n(4));
   if (kind == "greedy_step") return (int64_t)kw_greedy_step_workspace(n(0));
+  if (kind == "sample_step") return (int64_t)kw_sample_step_workspace(n(0));
   if (kind == "lm_greedy") return (int64_t)kw_dec_lm_greedy_workspace(n(0), n(1));
   if (kind == "qkv_self") return (int64_t)kw_dec_qkv_self_workspace(n(0), n(1));
   if (kind == "xq_cross") return (int64_t)kw_dec_xq_cross_workspace(n(0), n(1), n(2), n(3));
@@ -552,6 +610,10 @@ TORCH_LIBRARY(kw, m) {
   m.def("greedy_step(Tensor(a!) logits, Tensor suppress_mask, Tensor? begin_suppress, Tensor(b!) ids, "
         "Tensor(c!) cur_len, Tensor(d!) unfinished, Tensor(e!) counter, Tensor(f!) n_unfinished, "
         "Tensor(g!)? scores_out, Tensor(h!)? workspace, int[] cfg) -> ()");
+  m.def("sample_step(Tensor logits, Tensor suppress_mask, Tensor? begin_suppress, Tensor(a!) ids, Tensor(b!) cur_len, "
+        "Tensor(c!) unfinished, Tensor(d!) counter, Tensor(e!) n_unfinished, Tensor inv_temperature, Tensor seed, "
+        "Tensor attempt, Tensor(f!) sum_logprob, Tensor(g!) n_tokens, Tensor? active, Tensor(h!)? noise_out, "
+        "Tensor(i!) workspace, int[] cfg) -> ()");
   m.def("dec_lm_greedy(Tensor x, Tensor W, Tensor? bias, Tensor ln_colsum, Tensor(a!)? logits, Tensor suppress_mask, "
         "Tensor? begin_suppress, Tensor(b!) ids, Tensor(c!) cur_len, Tensor(d!) unfinished, Tensor(e!) n_unfinished, "
         "Tensor(f!) workspace, int[] lm_geo, float ln_eps, int[] cfg) -> ()");
@@ -582,6 +644,7 @@ TORCH_LIBRARY_IMPL(kw, CUDA, m) {
   m.impl("dec_qkv_self", &dec_qkv_self);
   m.impl("dec_xq_cross", &dec_xq_cross);
   m.impl("greedy_step", &greedy_step);
+  m.impl("sample_step", &sample_step);
   m.impl("dec_lm_greedy", &dec_lm_greedy);
   m.impl("beam_logprobs", &beam_logprobs);
   m.impl("beam_select", &beam_select);

@@ -20,7 +20,7 @@ LIB_PATH = os.environ.get("KWHISPER_LIB") or os.path.join(os.path.dirname(os.pat
 TORCH_LIB_PATH = os.environ.get("KWHISPER_TORCH_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)),
                                                                       "libkwhisper_torch.so")
 TORCH_OPS = ("log_mel", "mel_to_time_major", "gemm", "dec_linear", "pack_weight", "layernorm", "attention", "embed",
-             "self_attn_step", "dec_qkv_self", "dec_xq_cross", "cross_attn_step", "greedy_step", "dec_lm_greedy",
+             "self_attn_step", "dec_qkv_self", "dec_xq_cross", "cross_attn_step", "greedy_step", "sample_step", "dec_lm_greedy",
              "beam_logprobs", "beam_select", "align_capture", "align_weights", "align_reduce", "dtw")
 
 KW_OK, KW_EINVAL, KW_EHIP, KW_EUNSUPPORTED = 0, 1, 2, 3
@@ -88,6 +88,22 @@ class SamplerArgs(ctypes.Structure):
     ]
 
 
+class SampleArgs(ctypes.Structure):
+    _fields_ = [
+        ("logits", c_vp), ("B", c_i64), ("V", c_i64),
+        ("suppress_mask", c_vp), ("begin_suppress", c_vp), ("n_begin_suppress", c_i32),
+        ("return_timestamps", c_i32),
+        ("ts_begin", c_i32), ("no_ts_id", c_i32), ("eos_id", c_i32), ("pad_id", c_i32),
+        ("max_initial_ts", c_i32),
+        ("ids", c_vp), ("ids_stride", c_i64),
+        ("cur_len", c_vp), ("max_length", c_i32), ("begin_index", c_i32),
+        ("unfinished", c_vp), ("counter", c_vp), ("n_unfinished", c_vp),
+        ("inv_temperature", c_vp), ("seed", c_vp), ("attempt", c_vp),
+        ("sum_logprob", c_vp), ("n_tokens", c_vp), ("active", c_vp), ("noise_out", c_vp),
+        ("workspace", c_vp), ("ws_bytes", ctypes.c_size_t),
+    ]
+
+
 class BeamLogprobsArgs(ctypes.Structure):
     _fields_ = [
         ("logits", c_vp), ("R", c_i64), ("V", c_i64),
@@ -145,6 +161,8 @@ EXPORTS = {
     "kw_cross_attn_status_offset": (ctypes.c_size_t, [c_i64, c_i64, c_i64, c_i64, c_i64]),
     "kw_greedy_step": (ctypes.c_int, [ctypes.POINTER(SamplerArgs), c_vp]),
     "kw_greedy_step_workspace": (ctypes.c_size_t, [c_i64]),
+    "kw_sample_step": (ctypes.c_int, [ctypes.POINTER(SampleArgs), c_vp]),
+    "kw_sample_step_workspace": (ctypes.c_size_t, [c_i64]),
     "kw_dec_lm_greedy": (ctypes.c_int, [ctypes.POINTER(DecLinearArgs), ctypes.POINTER(SamplerArgs), c_vp]),
     "kw_dec_lm_greedy_workspace": (ctypes.c_size_t, [c_i64, c_i64]),
     "kw_dec_lm_greedy_supported": (ctypes.c_int, [c_i64, c_i64, c_i64]),

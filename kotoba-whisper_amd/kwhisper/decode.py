@@ -115,6 +115,8 @@ class DecodeSession:
         self._lmg_ws = None  # kw_dec_lm_greedy's partials + arrival counter (zeroed once; launches re-arm it)
         self.lm_greedy_last = False
         self.last_steps = 0
+        self._sample_state = None  # kw_sample_step's device scalars and accumulators (made on first use)
+        self.avg_logprob = self.n_tokens = None  # per row, left by the last generate(sample=...)
         if enc is not None:
             self.set_encoder_output(enc)
 
@@ -409,8 +411,16 @@ class DecodeSession:
 
     def generate(self, prompt: torch.Tensor, gen, *, max_length: int, return_timestamps: bool,
                  check_every: int = 4, use_graph: bool = True, record_scores: bool = False, align=None,
-                 num_frames=None, median_filter_width: int = 7):
+                 num_frames=None, median_filter_width: int = 7, sample=None):
         """Greedy loop of GenerationMixin._sample (TF/generation/utils.py:2783-2941).
+
+        ``sample``: None (the greedy path, unchanged), or a dict -- ``temperature`` (0 = argmax), ``seed``, ``attempt``
+        and ``active`` (per-row flags, None = all) -- that selects the statistics path: every step's tail is
+        kw_dec_linear(lm) + kw_sample_step (never the fused LM-head + greedy launch), which draws the token at that
+        temperature and accumulates each row's log-probability.  The call then leaves ``self.avg_logprob`` (float64) and
+        ``self.n_tokens`` per row (_retrieve_avg_logprobs, TF generation_whisper.py:1958-1974).  Inactive rows come back
+        as prompt + pad.  Temperature, seed, attempt and the active flags are device scalars, so one captured graph
+        serves every attempt of a schedule.
 
         Returns host int64 ids (B, L) including the prompt, with L exactly the length the reference
         loop stops at (all rows finished or max_length).
@@ -439,12 +449,33 @@ class DecodeSession:
         self.unfinished.fill_(1)
         self.counter.zero_()
         self.n_unfinished.fill_(B)
+        active = None
+        if sample is not None:
+            if align is not None or self.nb != 1:
+                raise NotImplementedError("sampling / statistics with token timestamps or beam search")
+            ss = self._sample_buffers()
+            t = float(sample.get("temperature") or 0.0)
+            ss["inv_t"].fill_(1.0 / t if t > 0.0 else 0.0)
+            seed = int(sample.get("seed", 0)) & 0xFFFFFFFFFFFFFFFF
+            ss["seed"].fill_(seed - (1 << 64) if seed >= (1 << 63) else seed)  # (the same 64 bits, as int64)
+            att = int(sample.get("attempt", 0)) & 0xFFFFFFFF
+            ss["attempt"].fill_(att - (1 << 32) if att >= (1 << 31) else att)
+            ss["sum_lp"].zero_()
+            ss["n_tok"].zero_()
+            active = np.ones(B, bool) if sample.get("active") is None else np.asarray(sample["active"], bool)
+            if active.shape != (B,) or not active.any():
+                raise ValueError("sample['active'] must flag at least one of the session's rows")
+            ss["active"].copy_(torch.from_numpy(active.astype(np.uint8)))
+            self.n_unfinished.fill_(int(active.sum()))
+        self.avg_logprob = self.n_tokens = None
         # the sampler plan, its processor tables and the captured step graph are kept per configuration:
         # a repeat call (the next batch) replays the same graph (no re-capture)
         key = (max_length, P, bool(return_timestamps), tuple(gen.suppress_tokens or ()),
                tuple(gen.begin_suppress_tokens or ()), gen.timestamp_begin, gen.no_timestamps_token_id,
                gen.eos_token_id, gen.pad_token_id, gen.max_initial_timestamp_index, bool(record_scores),
                self.eng.prefill_streams, self.eng.fuse_lm_greedy, align)
+        if sample is not None:
+            key += ("sample",)
         cfg = self._greedy_cfg.get(key)
         if cfg is None:
             sup = torch.zeros((self.eng.shape.vocab_size,), dtype=torch.uint8)
@@ -453,14 +484,19 @@ class DecodeSession:
             sup = sup.to(dev)
             bsup = torch.tensor(gen.begin_suppress_tokens or [0], dtype=torch.int32, device=dev)
             nb = len(gen.begin_suppress_tokens or [])
-            score_buf = torch.empty_like(self.logits) if record_scores else None
-            sampler = ops.SamplerPlan(self.logits, sup, bsup if nb else None, self.ids, self.cur_len,
-                                      self.unfinished, self.counter, self.n_unfinished,
-                                      return_timestamps=return_timestamps, ts_begin=gen.timestamp_begin,
-                                      no_ts_id=gen.no_timestamps_token_id, eos_id=gen.eos_token_id,
-                                      pad_id=gen.pad_token_id, max_initial_ts=gen.max_initial_timestamp_index,
-                                      max_length=max_length, begin_index=P, scores_out=score_buf,
-                                      workspace=self.samp_ws)
+            score_buf = torch.empty_like(self.logits) if record_scores and sample is None else None
+            pcfg = dict(return_timestamps=return_timestamps, ts_begin=gen.timestamp_begin,
+                        no_ts_id=gen.no_timestamps_token_id, eos_id=gen.eos_token_id, pad_id=gen.pad_token_id,
+                        max_initial_ts=gen.max_initial_timestamp_index, max_length=max_length, begin_index=P)
+            if sample is not None:
+                sampler = ops.SamplePlan(self.logits, sup, bsup if nb else None, self.ids, self.cur_len,
+                                         self.unfinished, self.counter, self.n_unfinished, inv_temperature=ss["inv_t"],
+                                         seed=ss["seed"], attempt=ss["attempt"], sum_logprob=ss["sum_lp"],
+                                         n_tokens=ss["n_tok"], active=ss["active"], workspace=ss["ws"], **pcfg)
+            else:
+                sampler = ops.SamplerPlan(self.logits, sup, bsup if nb else None, self.ids, self.cur_len,
+                                          self.unfinished, self.counter, self.n_unfinished, scores_out=score_buf,
+                                          workspace=self.samp_ws, **pcfg)
             cfg = dict(sampler=sampler, score_buf=score_buf, graph=None)
             if len(self._greedy_cfg) >= 8:  # bound the cache (each entry may hold a graph)
                 self._greedy_cfg.pop(next(iter(self._greedy_cfg)))
@@ -483,7 +519,7 @@ class DecodeSession:
         else:
             prefill()
         if record_scores:
-            self.scores.append((self.logits.clone(), score_buf.clone()))
+            self.scores.append((self.logits.clone(), score_buf.clone() if score_buf is not None else None))
         n_steps = max_length - P  # tokens the reference can add at most
         done = 1
         fused = max_length <= 256  # every step's position < 256 (kw_dec_qkv_self's key range)
@@ -493,7 +529,7 @@ class DecodeSession:
         tail = sampler
         s = self.eng.shape
         if (self.eng.packed and self.nb == 1 and self.eng.fuse_lm_greedy and not return_timestamps and not record_scores
-                and ops.lm_greedy_supported(B, s.vocab_size, s.d_model)):
+                and sample is None and ops.lm_greedy_supported(B, s.vocab_size, s.d_model)):
             tail = cfg.get("lm_greedy")
             if tail is None:
                 if self._lmg_ws is None:
@@ -548,7 +584,7 @@ class DecodeSession:
                     one_step()
                 done += 1
             if record_scores:
-                self.scores.append((self.logits.clone(), score_buf.clone()))
+                self.scores.append((self.logits.clone(), score_buf.clone() if score_buf is not None else None))
             if self._poll(pinned, events, rep, lag, self.n_unfinished):
                 break
             rep += 1
@@ -557,11 +593,42 @@ class DecodeSession:
         self.check_handoffs()
         L_now = int(self.cur_len.item())
         ids = self.ids[:, :L_now].cpu().numpy()
-        ids = _reference_length(ids, P, gen.eos_token_id, max_length)
+        if sample is not None:
+            # the length the reference stops at is that of the rows it decodes: the active ones
+            ids = ids[:, : _reference_length(ids[active], P, gen.eos_token_id, max_length).shape[1]]
+            n = ss["n_tok"].cpu().numpy().astype(np.int64)
+            with np.errstate(invalid="ignore", divide="ignore"):
+                self.avg_logprob = ss["sum_lp"].cpu().numpy().astype(np.float64) / n
+            self.n_tokens = n
+        else:
+            ids = _reference_length(ids, P, gen.eos_token_id, max_length)
         if align is not None:
             # the steps the reference ran: one per generated token but the last (not the poll lag's extra replays)
             self.align_out = self._alignment(align, ids.shape[1] - P - 1, num_frames, median_filter_width)
         return ids
+
+    def _sample_buffers(self):
+        """kw_sample_step's device scalars (1 / temperature, seed, attempt), per-row accumulators and active flags, and
+        its workspace; kept for the session's lifetime (plans and captured graphs hold their addresses)."""
+        if self._sample_state is None:
+            dev, R = self.eng.device, self.R
+            self._sample_state = dict(
+                inv_t=torch.zeros((1,), device=dev, dtype=torch.float32),
+                seed=torch.zeros((1,), device=dev, dtype=torch.int64),
+                attempt=torch.zeros((1,), device=dev, dtype=torch.int32),
+                sum_lp=torch.zeros((R,), device=dev, dtype=torch.float32),
+                n_tok=torch.zeros((R,), device=dev, dtype=torch.int32),
+                active=torch.ones((R,), device=dev, dtype=torch.uint8),
+                ws=torch.zeros((ops.sample_step_workspace_bytes(R) + 3) // 4, device=dev, dtype=torch.float32))
+        return self._sample_state
+
+    def no_speech_prob(self, sot: int, token: int, logits: torch.Tensor | None = None) -> np.ndarray:
+        """softmax of the raw logits at the <|startoftranscript|> position, at ``token`` (<|nospeech|>), per row
+        (WhisperNoSpeechDetection, TF generation/logits_process.py:2050-2112); the softmax runs on the device.
+        ``logits``: that position's logits if a caller (language detection) already has them."""
+        if logits is None:
+            logits = self.forward_logits(torch.full((self.B, 1), sot, dtype=torch.int64, device=self.eng.device))
+        return torch.softmax(logits.float(), -1)[:, token].cpu().numpy().astype(np.float64)
 
     def _alignment(self, align, T: int, num_frames, width: int):
         """weights -> reduce -> DTW over the first ``T`` logged steps; the host receives (B, T) frame indices."""

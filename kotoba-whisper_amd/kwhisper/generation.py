@@ -16,11 +16,29 @@ TF/models/whisper/generation_whisper.py:383-968):
   * ``num_beams`` > 1: GenerationMixin._beam_search on device (TF/generation/utils.py:3208-3527)
   * ``return_token_timestamps``: the alignment heads' cross-attention weights, their normalisation and the
     dynamic time warping on device (csrc/token_ts.hip)                :241-381, :1146-1157, :1685-1700
+  * the decoding fallback -- ``temperature`` (a float or a schedule), ``compression_ratio_threshold``,
+    ``logprob_threshold``, ``no_speech_threshold``: per seek pass the attempt loop of ``generate_with_fallback``, every
+    row's ``_need_fallback`` decision, the no-speech skip; tokens drawn and log-probabilities accumulated on device
+    (kw_sample_step, csrc/sampling.hip)                               :970-1116, :1243-1287, :876-881, :1949-1974
+
+Deliberate differences of the fallback from transformers 5.15.0:
+  * ``no_speech_threshold`` without ``logprob_threshold`` raises ``ValueError`` (the reference dies on an unbound local);
+  * ``temperature=None`` together with a threshold is treated as 0.0 (the reference raises ``TypeError``);
+  * every decision is made with the row's own numbers.  The reference indexes ``should_skip`` and ``no_speech_prob`` by
+    the row's position in the *current* attempt's batch, so once rows have left the fallback set it reads and writes
+    other rows' entries; the two agree while no row is skipped after the first attempt;
+  * a row's tokens are counted up to and including its first EOS; the reference counts pad tokens anywhere in the row
+    when it strips the padding (:1063-1071), which differs only for a padded row that also sampled the pad token;
+  * sampled tokens come from the engine's own counter-based generator (``manual_seed``), so they are distributed as
+    the reference's (softmax(s / T), multinomial) but are not the same draws as torch's.
 """
 from __future__ import annotations
 
 import copy
+import itertools
+import math
 import os
+import zlib
 from dataclasses import dataclass
 
 import numpy as np
@@ -89,6 +107,11 @@ class KWhisperForConditionalGeneration:
         self.record_alignment = False
         self._memo = None  # generate_multitask's per-batch encoder memo
         self._memo_count = 0
+        # sampling: kw_sample_step's Philox key is the seed; its attempt word is (lane << 24) | a counter that advances on
+        # every sampled decode, so attempts, passes and lane() handles all draw from distinct streams
+        self._seed, self._attempts, self._lane = 0, 0, 0
+        self._lane_ids = itertools.count(1)  # shared by every handle lane() makes from this one
+        self._sot_logits = None  # detect_language's raw logits at <|startoftranscript|>, for the no-speech probability
 
     # ---- nn.Module-ish surface used by callers ---------------------------------------------------
     @property
@@ -113,7 +136,15 @@ class KWhisperForConditionalGeneration:
         sessions) for running another batch at the same time from another host thread."""
         other = type(self)(self.engine.lane())
         other.generation_config = copy.deepcopy(self.generation_config)
+        other._seed, other._lane_ids = self._seed, self._lane_ids
+        other._lane = next(self._lane_ids)
         return other
+
+    def manual_seed(self, seed: int) -> "KWhisperForConditionalGeneration":
+        """Seed the sampler of the temperature fallback (default 0) and restart its attempt counter: the same calls
+        after the same ``manual_seed`` draw the same tokens."""
+        self._seed, self._attempts = int(seed), 0
+        return self
 
     @classmethod
     def from_state_dict(cls, shape, state_dict, *, dtype=torch.bfloat16, device="cuda", generation_config=None):
@@ -171,18 +202,42 @@ class KWhisperForConditionalGeneration:
             )
         if logits_processor or stopping_criteria:
             raise NotImplementedError("custom logits_processor / stopping_criteria are not supported on device")
-        for k in ("prompt_ids", "prefix_allowed_tokens_fn", "compression_ratio_threshold", "logprob_threshold",
-                  "no_speech_threshold", "assistant_model"):
+        for k in ("prompt_ids", "prefix_allowed_tokens_fn", "assistant_model", "output_scores"):
             if kwargs.get(k) is not None and kwargs.get(k) is not False:
                 raise NotImplementedError(f"`{k}` is not supported by the MI355X engine yet")
-        if kwargs.get("temperature") not in (None, 0, 0.0) or kwargs.get("do_sample"):
-            raise NotImplementedError("sampling / temperature fallback is not supported (greedy and beam only)")
         if kwargs.get("num_return_sequences") not in (None, 1):
             raise NotImplementedError("num_return_sequences > 1 is not supported")
         gen: GenerationConstants = copy.deepcopy(generation_config or self.generation_config)
         if isinstance(gen, dict):
             gen = GenerationConstants(**gen)
         num_beams = kwargs.get("num_beams", gen.num_beams or 1)
+        # decoding fallback: the thresholds from the call or the generation config (_set_thresholds_and_condition,
+        # generation_whisper.py:1703-1729) and the temperature schedule (:735); `do_sample` itself is overridden by
+        # the schedule (:1002-1010)
+        thr = {k: kwargs.get(k) if kwargs.get(k) is not None else getattr(gen, k, None)
+               for k in ("compression_ratio_threshold", "logprob_threshold", "no_speech_threshold")}
+        cond_prev = kwargs.get("condition_on_prev_tokens")
+        if cond_prev is None:
+            cond_prev = getattr(gen, "condition_on_prev_tokens", None)
+        if cond_prev:
+            raise NotImplementedError("`condition_on_prev_tokens=True` is not supported by the MI355X engine yet")
+        temperature = kwargs.get("temperature")
+        temperatures = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature]
+        has_thr = any(v is not None for v in thr.values())
+        fallback = has_thr or any(t is not None and t > 0.0 for t in temperatures)
+        if fallback:
+            if thr["no_speech_threshold"] is not None and thr["logprob_threshold"] is None:
+                raise ValueError("`no_speech_threshold` needs `logprob_threshold`: a window is skipped only when its "
+                                 "average log-probability is below `logprob_threshold` as well")
+            temperatures = [0.0 if t is None else float(t) for t in temperatures]
+            if not temperatures:
+                raise ValueError("`temperature` must be a number or a non-empty sequence of numbers")
+            if num_beams > 1:
+                raise NotImplementedError("the decoding fallback (thresholds or a temperature above 0) with `num_beams` "
+                                          "> 1 is not supported by the MI355X engine yet; use num_beams=1")
+            if kwargs.get("return_token_timestamps"):
+                raise NotImplementedError("the decoding fallback (thresholds or a temperature above 0) with "
+                                          "`return_token_timestamps` is not supported by the MI355X engine yet")
         if num_beams > 8:
             raise NotImplementedError("num_beams > 8 is not supported by the device beam search")
         length_penalty = kwargs.get("length_penalty", getattr(gen, "length_penalty", 1.0))
@@ -238,6 +293,7 @@ class KWhisperForConditionalGeneration:
             raise ValueError("Cannot specify `task` or `language` for an English-only model.")
 
         # prompt (init tokens)
+        self._sot_logits = None
         prompt_all = self._init_tokens(gen, B, language, task, return_timestamps, feats, enc_given)
         P = prompt_all.shape[1]
 
@@ -266,6 +322,7 @@ class KWhisperForConditionalGeneration:
         row_passes = np.zeros(B, dtype=np.int64)
         pass_log, pass_ids = [], []  # per pass: (rows, their seek, their frame count); the decoded ids
         align_log, last_ts = [], None
+        fallback_log = []
         while (seek < max_frames).any():
             batch_map = [p for p in batch_map if seek[p] < max_frames[p]]
             cur = len(batch_map)
@@ -304,7 +361,16 @@ class KWhisperForConditionalGeneration:
                 eff_max = P + max_new_tokens
             sess = self._session(cur, num_beams)
             sess.set_encoder_output(enc, key=enc_key)
-            if num_beams > 1:
+            skip = [False] * cur
+            if fallback:
+                sot = None
+                if passes == 0 and feats is not None and whole and self._sot_logits is not None \
+                        and self._sot_logits.shape[0] == cur:
+                    sot = self._sot_logits  # language detection ran this very position on these features
+                ids, skip, attempts = self._generate_with_fallback(sess, prompt, gen, eff_max, return_timestamps,
+                                                                   temperatures, thr, batch_map, sot)
+                fallback_log.append(attempts)
+            elif num_beams > 1:
                 ids = sess.generate_beam(torch.from_numpy(prompt), gen, num_beams=num_beams, max_length=eff_max,
                                          return_timestamps=return_timestamps, length_penalty=length_penalty,
                                          early_stopping=early_stopping)
@@ -329,6 +395,9 @@ class KWhisperForConditionalGeneration:
                 pass_ids.append(np.asarray(ids).copy())
             pad, eos = gen.pad_token_id, gen.eos_token_id
             for i, p in enumerate(batch_map):
+                if skip[i]:  # a no-speech window: no segment, the seek moves on (generation_whisper.py:876-881)
+                    seek[p] += seek_num[p]
+                    continue
                 seq = _strip_pass_row(ids[i, P:], pad, eos)
                 segs, off = _retrieve_segment(seq, ts_begin, int(seek_num[p]), float(time_offset[p]),
                                               token_ts=(pass_ts[i], ids[i], P) if token_ts else None)
@@ -341,6 +410,8 @@ class KWhisperForConditionalGeneration:
             self.stats["pass_ids"] = pass_ids
         if token_ts and self.record_alignment:
             self.stats["alignment"] = align_log
+        if fallback:
+            self.stats["fallback"] = fallback_log
         if return_dict_in_generate and not return_timestamps:
             res = {"sequences": torch.from_numpy(last_ids).to(eng.device)}
             if token_ts:  # _stack_split_outputs: the single pass's timestamps, prompt positions included
@@ -363,6 +434,56 @@ class KWhisperForConditionalGeneration:
         if return_segments or (return_dict_in_generate and return_timestamps):
             return {"sequences": res, "segments": segments}
         return res
+
+    def _generate_with_fallback(self, sess, prompt, gen, max_length, return_timestamps, temperatures, thr, batch_map,
+                                sot_logits=None):
+        """One seek pass's attempt loop (``generate_with_fallback``, generation_whisper.py:1001-1116): decode at each
+        temperature of the schedule in turn -- 0 greedy, above 0 sampled -- re-decoding only the rows whose
+        ``_need_fallback`` decision asks for it, in the same session (its cross K/V stays; no re-encode); the last
+        temperature's result is accepted.  Returns the pass's ids (cur, L) with every row from the attempt that was
+        accepted for it (right-padded), the rows to skip, and the per-attempt record kept in ``stats["fallback"]``."""
+        cur, P = prompt.shape
+        pad, eos, V = gen.pad_token_id, gen.eos_token_id, self.engine.shape.vocab_size
+        nsp = None
+        if thr["no_speech_threshold"] is not None:
+            nsp = sess.no_speech_prob(gen.decoder_start_token_id, gen.no_timestamps_token_id - 1, sot_logits)
+        rows = list(range(cur))
+        final = [None] * cur
+        skip = [False] * cur
+        attempts = []
+        for ai, t in enumerate(temperatures):
+            if t > 0.0:
+                self._attempts += 1
+            active = np.zeros(cur, bool)
+            active[rows] = True
+            ids = sess.generate(torch.from_numpy(prompt), gen, max_length=max_length, return_timestamps=return_timestamps,
+                                sample=dict(temperature=t, seed=self._seed, active=active,
+                                            attempt=(self._lane << 24) | (self._attempts & 0xFFFFFF)))
+            rec = dict(rows=[int(batch_map[i]) for i in rows], temperature=float(t), avg_logprob=[], compression_ratio=[],
+                       no_speech_prob=[], needs_fallback=[], should_skip=[])
+            again = []
+            for i in rows:
+                # the row's tokens without the padding but with its EOS (:1063-1071)
+                seq = _strip_pass_row(ids[i, P:], pad, eos, keep_eos=True)
+                cr = _compression_ratio(seq, V) if thr["compression_ratio_threshold"] is not None else None
+                lp = float(sess.avg_logprob[i])
+                p_ns = float(nsp[i]) if nsp is not None else None
+                needs, skips = _need_fallback(cr, lp, p_ns, thr)
+                for k, v in (("avg_logprob", lp), ("compression_ratio", cr), ("no_speech_prob", p_ns),
+                             ("needs_fallback", needs), ("should_skip", skips)):
+                    rec[k].append(v)
+                final[i], skip[i] = ids[i], skips
+                if needs:
+                    again.append(i)
+            attempts.append(rec)
+            rows = again
+            if not rows:
+                break
+        longest = max(len(r) for r in final)
+        out = np.full((cur, longest), pad, dtype=np.int64)
+        for i, r in enumerate(final):
+            out[i, : len(r)] = r
+        return out, skip, attempts
 
     def generate_multitask(self, input_features, tasks, **kwargs):
         """``generate`` once per (language, task) of ``tasks`` on the same features -- the inner loop of
@@ -398,6 +519,7 @@ class KWhisperForConditionalGeneration:
         sess.set_encoder_output(enc)
         prompt = torch.full((B, 1), gen.decoder_start_token_id, dtype=torch.int64, device=eng.device)
         logits = sess.forward_logits(prompt).clone()
+        self._sot_logits = logits.clone()
         mask = torch.ones(logits.shape[-1], dtype=torch.bool, device=logits.device)
         mask[list(gen.lang_to_id.values())] = False
         logits[:, mask] = -float("inf")
@@ -447,17 +569,40 @@ class KWhisperForConditionalGeneration:
         return np.broadcast_to(arr, (B, arr.shape[1])).copy()
 
 
-def _strip_pass_row(seq, pad, eos):
-    """A pass's generated tokens of one row without its padding and its EOS (generation_whisper.py:1063-1086)."""
+def _strip_pass_row(seq, pad, eos, keep_eos=False):
+    """A pass's generated tokens of one row without its padding and its EOS (generation_whisper.py:1063-1086);
+    ``keep_eos``: with the EOS, as ``_need_fallback`` takes them."""
     if seq.size and seq[-1] == pad:
         n = int((seq == pad).sum())
         if pad == eos:
             n -= 1
         if n != 0:
             seq = seq[:-n]
-    if seq.size and seq[-1] == eos:
+    if not keep_eos and seq.size and seq[-1] == eos:
         seq = seq[:-1]
     return seq
+
+
+def _compression_ratio(tokens, vocab_size):
+    """``_retrieve_compression_ratio`` (generation_whisper.py:1949-1955): the tokens' bytes over their zlib size."""
+    length = int(math.log2(vocab_size) / 8) + 1
+    token_bytes = b"".join([int(t).to_bytes(length, "little") for t in tokens.tolist()])
+    return len(token_bytes) / len(zlib.compress(token_bytes))
+
+
+def _need_fallback(compression_ratio, avg_logprob, no_speech_prob, thr):
+    """``_need_fallback`` (generation_whisper.py:1243-1287) on one row's numbers -> (needs_fallback, should_skip); a
+    skip cancels a fallback."""
+    needs_fallback = should_skip = False
+    if thr["compression_ratio_threshold"] is not None and compression_ratio > thr["compression_ratio_threshold"]:
+        needs_fallback = True
+    if thr["logprob_threshold"] is not None and avg_logprob < thr["logprob_threshold"]:
+        needs_fallback = True
+    if thr["no_speech_threshold"] is not None:
+        if avg_logprob < thr["logprob_threshold"] and no_speech_prob > thr["no_speech_threshold"]:
+            needs_fallback = False
+            should_skip = True
+    return needs_fallback, should_skip
 
 
 def _pad_token_timestamps(segments, longest):

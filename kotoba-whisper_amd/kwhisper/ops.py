@@ -5,7 +5,7 @@ ops wrap the ABI"), which fills the C ABI's argument block and launches on torch
 the kernels are ordinary torch ops to the dispatcher, to ``torch.cuda.graph`` capture and to
 ``torch.compile`` (fake implementations are registered: every op mutates its outputs and returns nothing).
 Tensors are plumbing only (device memory + stream); all arithmetic happens in the HIP kernels of
-``libkwhisper.so``.  The plan classes (``GemmPlan``, ``DecLinearPlan``, ``SamplerPlan``, ``BeamStepPlan``)
+``libkwhisper.so``.  The plan classes (``GemmPlan``, ``DecLinearPlan``, ``SamplerPlan``, ``SamplePlan``, ``BeamStepPlan``)
 validate once and keep the op arguments, so decode steps replay without re-validation.
 
 ``set_backend("ctypes")`` routes the same calls through the ctypes binding of the C ABI instead (used by
@@ -71,7 +71,7 @@ def _ws_bytes(kind: str, *dims) -> int:
         return int(_kw().workspace_bytes(kind, [int(d) for d in dims]))
     fn = {"dec_linear": "kw_dec_linear_workspace_bytes", "packed_weight": "kw_packed_weight_bytes",
           "self_attn": "kw_self_attn_workspace", "cross_attn": "kw_cross_attn_workspace",
-          "greedy_step": "kw_greedy_step_workspace", "beam_logprobs": "kw_beam_logprobs_workspace",
+          "greedy_step": "kw_greedy_step_workspace", "sample_step": "kw_sample_step_workspace", "beam_logprobs": "kw_beam_logprobs_workspace",
           "lm_greedy": "kw_dec_lm_greedy_workspace", "dtw": "kw_dtw_workspace",
           "qkv_self": "kw_dec_qkv_self_workspace", "xq_cross": "kw_dec_xq_cross_workspace",
           "qkv_self_status": "kw_dec_qkv_self_status_offset", "xq_cross_status": "kw_dec_xq_cross_status_offset",
@@ -532,6 +532,74 @@ class SamplerPlan:
             _kw().greedy_step(*self._targs)
         else:
             L.check(_lib().kw_greedy_step(self._ref, _s()), "kw_greedy_step")
+
+
+def sample_step_workspace_bytes(B: int) -> int:
+    return _ws_bytes("sample_step", B)
+
+
+class SamplePlan:
+    """Pre-built ``kw_sample_step`` call: ``SamplerPlan``'s processors, stopping and device state, the token drawn at
+    the temperature the device scalar ``inv_temperature`` (f32 [1], 0 = argmax) names with Philox noise keyed by
+    ``seed`` (int64 [1]) and ``attempt`` (int32 [1]), and each unfinished row's token log-probability added to
+    ``sum_logprob`` (f32 [B]) / ``n_tokens`` (int32 [B]).  ``active`` (uint8 [B], optional): rows with 0 are finished
+    from the first step; ``noise_out`` (f32 [B][V], optional): the noise used; ``workspace`` zero-filled
+    (sample_step_workspace_bytes)."""
+
+    def __init__(self, logits, suppress_mask, begin_suppress, ids, cur_len, unfinished, counter, n_unfinished, *,
+                 inv_temperature, seed, attempt, sum_logprob, n_tokens, workspace, return_timestamps, ts_begin, no_ts_id,
+                 eos_id, pad_id, max_initial_ts, max_length, begin_index, active=None, noise_out=None):
+        ts = (logits, suppress_mask, begin_suppress, ids, cur_len, unfinished, counter, n_unfinished, inv_temperature,
+              seed, attempt, sum_logprob, n_tokens, active, noise_out, workspace)
+        _cuda(*ts)
+        B, V = logits.shape
+        if logits.dtype != torch.float32 or not logits.is_contiguous():
+            raise ValueError("kw_sample_step takes contiguous float32 logits")
+        if (inv_temperature.dtype != torch.float32 or seed.dtype != torch.int64 or attempt.dtype != torch.int32
+                or sum_logprob.dtype != torch.float32 or n_tokens.dtype != torch.int32 or sum_logprob.numel() < B
+                or n_tokens.numel() < B):
+            raise ValueError("kw_sample_step: inv_temperature f32 [1], seed int64 [1], attempt int32 [1], sum_logprob "
+                             "f32 [B], n_tokens int32 [B]")
+        if active is not None and (active.dtype != torch.uint8 or active.numel() < B):
+            raise ValueError("kw_sample_step: active must be uint8 [B]")
+        if noise_out is not None and (noise_out.dtype != torch.float32 or not noise_out.is_contiguous()
+                                      or noise_out.numel() < B * V):
+            raise ValueError("kw_sample_step: noise_out must be a contiguous float32 [B][V] tensor")
+        if (suppress_mask.numel() < V or unfinished.numel() < B or ids.shape[0] < B or ids.stride(1) != 1
+                or ids.shape[1] < max_length):
+            raise ValueError("kw_sample_step: suppress_mask [V], unfinished [B], ids [B][>= max_length]")
+        if workspace.numel() * workspace.element_size() < sample_step_workspace_bytes(B):
+            raise ValueError("kw_sample_step workspace too small")
+        self._keep = ts
+        mit = -1 if max_initial_ts is None else max_initial_ts
+        cfg = [int(bool(return_timestamps)), ts_begin, no_ts_id, eos_id, pad_id, mit, max_length, begin_index]
+        self._targs = (logits, suppress_mask, begin_suppress, ids, cur_len, unfinished, counter, n_unfinished,
+                       inv_temperature, seed, attempt, sum_logprob, n_tokens, active, noise_out, workspace, cfg)
+        a = L.SampleArgs()
+        a.logits = logits.data_ptr()
+        a.B, a.V = B, V
+        a.suppress_mask = suppress_mask.data_ptr()
+        a.begin_suppress = begin_suppress.data_ptr() if begin_suppress is not None else None
+        a.n_begin_suppress = begin_suppress.numel() if begin_suppress is not None else 0
+        a.return_timestamps = int(bool(return_timestamps))
+        a.ts_begin, a.no_ts_id, a.eos_id, a.pad_id = ts_begin, no_ts_id, eos_id, pad_id
+        a.max_initial_ts = mit
+        a.ids, a.ids_stride, a.cur_len = ids.data_ptr(), ids.stride(0), cur_len.data_ptr()
+        a.max_length, a.begin_index = max_length, begin_index
+        a.unfinished, a.counter, a.n_unfinished = unfinished.data_ptr(), counter.data_ptr(), n_unfinished.data_ptr()
+        a.inv_temperature, a.seed, a.attempt = inv_temperature.data_ptr(), seed.data_ptr(), attempt.data_ptr()
+        a.sum_logprob, a.n_tokens = sum_logprob.data_ptr(), n_tokens.data_ptr()
+        a.active = active.data_ptr() if active is not None else None
+        a.noise_out = noise_out.data_ptr() if noise_out is not None else None
+        a.workspace, a.ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+        self.args = a
+        self._ref = ctypes.byref(a)
+
+    def __call__(self):
+        if _BACKEND == "torch":
+            _kw().sample_step(*self._targs)
+        else:
+            L.check(_lib().kw_sample_step(self._ref, _s()), "kw_sample_step")
 
 
 def lm_greedy_workspace_bytes(B: int, V: int) -> int:

@@ -683,6 +683,130 @@ def pipeline_fixtures(tags=("tiny", "tiny_longform", "kotoba_v2")):
         np.savez_compressed(os.path.join(GOLD, f"pipeline_{tag}{suffix}.npz"), **out)
 
 # ---- token-level timestamps (return_token_timestamps) ----------------------------------------------------------
+# ---- decoding fallback (temperature schedule, thresholds, no-speech skip) ------------------------------------------
+FALLBACK_CLIPS = [("dummy", 0), ("dummy", 1), ("tone", 0), ("tone", 1)]  # + one row of digital silence (the last)
+FALLBACK_SEED = 11  # torch's generator for the reference's sampled attempts
+# mode -> (generate kwargs, eos override).  (a): one temperature, all three thresholds, chosen so that the silent row
+# and no other is skipped; (b): a schedule, chosen so that some rows fall back and some do not.  The thresholds sit
+# between the values the seeded tiny model gives (fallback_fixtures asserts the margins).
+FALLBACK_MODES = {
+    "a_nots": (dict(return_timestamps=False, temperature=0.0, logprob_threshold=-1.0, compression_ratio_threshold=2.4,
+                    no_speech_threshold=8e-6), None),
+    "a_ts": (dict(return_timestamps=True, temperature=0.0, logprob_threshold=-1.0, compression_ratio_threshold=2.4,
+                  no_speech_threshold=8e-6), None),
+    "a_eos": (dict(return_timestamps=False, temperature=0.0, logprob_threshold=-1.0, compression_ratio_threshold=2.4,
+                   no_speech_threshold=8e-6), 7656),
+    "b_nots": (dict(return_timestamps=False, temperature=(0.0, 0.4), logprob_threshold=-4.2,
+                    compression_ratio_threshold=2.4), None),
+    "b_ts": (dict(return_timestamps=True, temperature=(0.0, 0.4), logprob_threshold=-5.0,
+                  compression_ratio_threshold=1.45), None),
+    "b_eos": (dict(return_timestamps=False, temperature=(0.0, 0.4), logprob_threshold=-4.2,
+                   compression_ratio_threshold=1.2, no_speech_threshold=8e-6), 7656),
+}
+FALLBACK_MAX_LENGTH = 40
+
+
+class _FallbackRecorder:
+    """Wraps one HF model's ``generate_with_fallback`` / ``_need_fallback`` and keeps, per seek pass and attempt, the
+    rows decoded and what every row's decision saw and returned."""
+
+    def __init__(self, m):
+        self.m, self.passes = m, []
+        self._gwf, self._nf = m.generate_with_fallback, m._need_fallback
+        m.generate_with_fallback, m._need_fallback = self.gwf, self.need
+
+    def close(self):
+        del self.m.generate_with_fallback, self.m._need_fallback
+
+    def gwf(self, **kw):
+        self.passes.append(dict(rows=[int(i) for i in kw["batch_idx_map"]], attempts=[]))
+        return self._gwf(**kw)
+
+    def need(self, seek_sequence, seek_outputs, index, logits_processor, generation_config, vocab_size, temperature):
+        from transformers.generation.logits_process import WhisperNoSpeechDetection
+
+        needs, skip = self._nf(seek_sequence, seek_outputs, index, logits_processor, generation_config, vocab_size,
+                               temperature)
+        ps = self.passes[-1]
+        if index == 0:  # every attempt walks its rows from 0
+            prev = ps["attempts"][-1] if ps["attempts"] else None
+            rows = ps["rows"] if prev is None else [r for r, n in zip(prev["rows"], prev["needs_fallback"]) if n]
+            ps["attempts"].append(dict(rows=rows, temperature=float(temperature), avg_logprob=[], compression_ratio=[],
+                                       no_speech_prob=[], needs_fallback=[], should_skip=[], tokens=[]))
+        at = ps["attempts"][-1]
+        nsp = [p.no_speech_prob for p in logits_processor if isinstance(p, WhisperNoSpeechDetection)]
+        at["avg_logprob"].append(float(self.m._retrieve_avg_logprobs(seek_outputs[index]["scores"], seek_sequence,
+                                                                     temperature)))
+        at["compression_ratio"].append(float(self.m._retrieve_compression_ratio(seek_sequence, vocab_size)))
+        # (the reference reads no_speech_prob at the row's position in the CURRENT batch; the fixture keeps the row's own)
+        at["no_speech_prob"].append(float(nsp[0][ps["rows"].index(at["rows"][index])]) if nsp else float("nan"))
+        at["needs_fallback"].append(bool(needs))
+        at["should_skip"].append(bool(skip))
+        at["tokens"].append([int(t) for t in seek_sequence.tolist()])
+        return needs, skip
+
+
+def fallback_features():
+    fe = WhisperFeatureExtractor(feature_size=TINY.num_mel_bins)
+    audio = [clip_audio(k, s) for k, s in FALLBACK_CLIPS] + [np.zeros(480000, np.float32)]
+    return torch.from_numpy(fe(audio, sampling_rate=16000, return_tensors="np")["input_features"])
+
+
+def fallback_run(m, feats, kw, eos):
+    gconf, _ = hf_gen_config(TINY)
+    if eos is not None:
+        gconf.eos_token_id = eos
+    m.generation_config = gconf
+    rec = _FallbackRecorder(m)
+    torch.manual_seed(FALLBACK_SEED)
+    try:
+        with torch.no_grad():
+            res = m.generate(feats, language="ja", task="transcribe", max_length=FALLBACK_MAX_LENGTH,
+                             return_segments=True, **kw)
+    finally:
+        rec.close()
+    return res, rec.passes
+
+
+def fallback_fixtures():
+    """tests/golden/fallback_tiny.npz: the decoding fallback through the real HF generate (tiny, fp32, CPU) -- per
+    mode the final sequences and segments, and per seek pass, attempt and row what ``_need_fallback`` saw and said."""
+    t0 = time.time()
+    m = hf_model(TINY)
+    feats = fallback_features()
+    silent = feats.shape[0] - 1
+    out = {"cases": np.array([f"{k}:{s}" for k, s in FALLBACK_CLIPS]), "max_length": FALLBACK_MAX_LENGTH,
+           "seed": FALLBACK_SEED}
+    for name, (kw, eos) in FALLBACK_MODES.items():
+        res, passes = fallback_run(m, feats, kw, eos)
+        lp_t, cr_t, ns_t = (kw.get(k) for k in ("logprob_threshold", "compression_ratio_threshold", "no_speech_threshold"))
+        skipped, fell = set(), set()
+        for ps in passes:
+            for ai, at in enumerate(ps["attempts"]):
+                for r, lp, cr, ns, nf, sk in zip(at["rows"], at["avg_logprob"], at["compression_ratio"],
+                                                 at["no_speech_prob"], at["needs_fallback"], at["should_skip"]):
+                    assert abs(lp - lp_t) >= 0.05, (name, r, lp)
+                    assert abs(cr - cr_t) >= 0.02, (name, r, cr)
+                    assert ns_t is None or ns >= 2 * ns_t or ns <= ns_t / 2, (name, r, ns)
+                    assert not sk or ai == 0, "a skip after the first attempt: the reference's row indexing is off there"
+                    if sk:
+                        skipped.add(r)
+                    if nf and ai == 0:
+                        fell.add(r)
+        if name.startswith("a_"):
+            assert skipped == {silent}, (name, skipped)
+        else:
+            rows = set(range(feats.shape[0])) - skipped
+            assert fell and fell < rows, (name, fell)
+        out[f"{name}_sequences"] = res["sequences"].numpy().astype(np.int64)
+        segs = [[(float(s["start"]), float(s["end"]), [int(t) for t in s["tokens"]]) for s in row] for row in res["segments"]]
+        out[f"{name}_segments"] = np.array(json.dumps(segs))
+        out[f"{name}_passes"] = np.array(json.dumps(passes))
+        print(f"  fallback:{name} {tuple(res['sequences'].shape)} skipped {sorted(skipped)} fell back {sorted(fell)} "
+              f"({time.time() - t0:.1f}s)")
+    np.savez_compressed(os.path.join(GOLD, "fallback_tiny.npz"), **out)
+
+
 TOKEN_TS_HEADS = [[2, 2], [3, 0], [3, 2], [3, 3], [3, 4], [3, 5]]
 TOKEN_TS_CLIPS = [("dummy", 0), ("tone", 1), ("dummy", 2), ("tone", 3)]
 TOKEN_TS_MASK = {1: 2000, 3: 1200}  # row -> valid feature frames (the others: all 3000)
@@ -839,6 +963,8 @@ def main():
         beam_fixtures()
     if a.only in (None, "token_ts"):
         token_ts_fixtures()
+    if a.only in (None, "fallback"):
+        fallback_fixtures()
     if a.only in (None, "longform"):
         longform_fixtures()
     if a.only in (None, "tiny"):
