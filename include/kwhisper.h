@@ -279,6 +279,70 @@ size_t kw_dec_qkv_self_status_offset(int64_t M, int64_t d);
 size_t kw_dec_xq_cross_status_offset(int64_t M, int64_t d, int64_t H, int64_t S);
 size_t kw_cross_attn_status_offset(int64_t B, int64_t q_len, int64_t H, int64_t hd, int64_t S);
 
+/* ---- fp8 cross K/V (additive, ABI 112 unchanged; opt-in: WhisperEngine(cross_kv_dtype="fp8_e4m3")) ----------
+ * The cross-attention K / V cache at one byte per element.  Format:
+ *   codes:  uint8 [2L][B][H][S][64], OCP e4m3fn (the gfx950 fp8; NOT the fnuz variant): the bf16 cache's layout.
+ *   scales: float32 [2L][B][H][64]: one per (K or V of a layer, item, head, head dim), taken over the S frames.
+ * From the bf16 values x that the cross-K/V GEMM wrote (kw_gemm, KW_EPI_HEADSPLIT), per channel:
+ *   a     = max_s |x|
+ *   scale = a / 448.0f
+ *   inv   = 448.0f / a            (one correctly rounded f32 division per channel)
+ *   a == 0:  scale = inv = 0 and every code 0
+ *   code  = e4m3_rne(x * inv)     (one f32 multiply, round to nearest even; |x * inv| exceeds 448 by f32 rounding
+ *                                  at most, and that rounds to 448)
+ *   dequantised value = float(code) * scale
+ * Non-finite K / V is out of scope.
+ *
+ * kw_cross_kv_quant: x bf16 [n][S][64] -> codes uint8 [n][S][64], scales f32 [n][64], n = the (K/V, layer, item, head)
+ * tiles of the call, any S >= 1; x and codes 16-B aligned.  Replaces nothing in TF (the reference keeps bf16): it
+ * follows the k_proj / v_proj of TF modeling_whisper.py:323-335 once per item. */
+int kw_cross_kv_quant(const void* x, int64_t n, int64_t S, int64_t hd, void* codes, float* scales, kw_stream_t stream);
+
+/* kw_cross_attn_step over the fp8 cache (TF modeling_whisper.py:323-356 on the dequantised K / V): q, out bf16
+ * [B*q_len][H*hd]; k / v: one layer's codes [B][H][S][64]; k_scale / v_scale: its scales [B][H][64].  f32 arithmetic
+ * on the decoded codes; K's scales multiply the query once (q'[i] = q[i] * log2(e) * s_k[i]), V's the output
+ * (o[i] * s_v[i] / l).  Differences from the bf16 dispatch:
+ *   - ONE grid at every batch size: one workgroup per (query row, head) pair streaming the pair's six chunks (the pair
+ *     kernel of kw_cross_attn_pair_kernel); no chunk grid, no multi-row kernel, no workspace, no hand-off, no status
+ *     word.  Small batches under-fill the device, large ones take several rounds; a row's output does not depend on
+ *     its batch.
+ *   - q_len > 1 (the prefill) runs as B * q_len * H pairs: query row r reads item r / q_len, so K / V is re-read once
+ *     per position.
+ *   - S must split into six chunks of 225..256 keys (1500: 6 x 250; 1399: 5 x 234 + 229; 1536: 6 x 256); anything
+ *     else, and hd != 64, is KW_EUNSUPPORTED with a message.
+ * q, k, v, k_scale 16-B aligned. */
+int kw_cross_attn_step_fp8(const void* q, int64_t B, int64_t q_len, int64_t H, int64_t hd, const void* k, const void* v,
+                           const float* k_scale, const float* v_scale, int64_t S, void* out, kw_stream_t stream);
+
+/* kw_dec_xq_cross over the fp8 cache: the LayerNorm-fused q projection and kw_cross_attn_step_fp8 (q_len 1) in ONE
+ * launch, bit for bit kw_dec_linear(xq) followed by kw_cross_attn_step_fp8.  Arguments as kw_dec_xq_cross_args with
+ * k / v one layer's codes [M][H][S][64] and k_scale / v_scale its scales [M][H][64].  The projection workgroups lead
+ * the grid; every wait is on work dispatched earlier in the same launch.  The workspace is kw_dec_xq_cross's:
+ * kw_dec_xq_cross_workspace(M, d, H, S) bytes, zero-filled before first use, with the status word and the
+ * fault-injection word at kw_dec_xq_cross_status_offset(M, d, H, S).  Shapes: M <= 32, d = 64 H <= 1280, S as
+ * kw_cross_attn_step_fp8 (kw_dec_xq_cross_fp8_supported(): 1 when covered; the pair grid at every M). */
+typedef struct {
+  const void* x;
+  int64_t ldx;
+  float ln_eps;
+  const float* ln_colsum;
+  const void* W;
+  const float* bias;
+  float scale;
+  int64_t M, d, H;
+  const void* k;
+  const void* v;
+  const float* k_scale;
+  const float* v_scale;
+  int64_t S;
+  void* out;
+  void* workspace;
+  size_t ws_bytes;
+} kw_dec_xq_cross_fp8_args;
+
+int kw_dec_xq_cross_fp8(const kw_dec_xq_cross_fp8_args* args, kw_stream_t stream);
+int kw_dec_xq_cross_fp8_supported(int64_t M, int64_t d, int64_t H, int64_t S);
+
 /* One greedy decoding step on f32 logits [B][V] (TF generation/utils.py:2894-2937):
  * SuppressTokens -> SuppressTokensAtBegin (when L == begin_index) -> WhisperTimeStamp (if
  * return_timestamps; TF generation/logits_process.py:1816-2047) -> argmax (first max) ->

@@ -1062,6 +1062,14 @@ struct CRP {
   ProjArgs proj;  // the query projection (rows M = proj.M), when it runs in the launch
 };
 
+// ... over the fp8 cache (cross_attn_row_fp8_kernel): kc / vc hold e4m3 codes, ks / vs one layer's scales
+// [items][H][64]; query row r reads item r / q_len
+struct CRP8 : CRP {
+  const float* ks;
+  const float* vs;
+  int q_len;
+};
+
 // ------------------------------------------------------------------------------------------------
 // The cross-attention block's query projection and attention step in ONE launch (bf16 engine, q_len 1):
 // the LayerNorm-fused q projection (TF/models/whisper/modeling_whisper.py:483 encoder_attn_layer_norm,
@@ -1118,11 +1126,17 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void x
 // a chunk's 16-B pieces of the pair's K or V rows (lane: row k0 + slot + 32 j, bytes voff = (slot * 64 + sub * 8) * 2
 // of it) through a buffer resource over the pair's S rows: rows past S read as 0 (masked like every row past the
 // chunk end), so no per-piece clamp or 64-bit address arithmetic -- one add per piece
-__device__ __forceinline__ void row_issue(__amdgpu_buffer_rsrc_t rs, int k0, uint32_t voff, u32x4 (&r)[8]) {
+template <typename P>  // P: a lane's piece of a row, 16 B of bf16 (u32x4) or 8 B of e4m3 codes (u32x2, voff / k0 in those rows' bytes)
+__device__ __forceinline__ void row_issue(__amdgpu_buffer_rsrc_t rs, int k0, uint32_t voff, P (&r)[8]) {
+  constexpr int RB = HD * (int)sizeof(P) / 8;  // bytes of a row
   __builtin_amdgcn_sched_barrier(0);  // issue exactly here: the schedule is the point (the compiler would sink these
 #pragma unroll                        // loads below the next chunk's arithmetic and wait on them there)
-  for (int j = 0; j < 8; ++j)
-    r[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff + (uint32_t)((k0 + 32 * j) * HD * 2), 0, 2));
+  for (int j = 0; j < 8; ++j) {
+    if constexpr (sizeof(P) == 16)
+      r[j] = __builtin_bit_cast(u32x4, __builtin_amdgcn_raw_buffer_load_b128(rs, voff + (uint32_t)((k0 + 32 * j) * RB), 0, 2));
+    else
+      r[j] = __builtin_bit_cast(u32x2, __builtin_amdgcn_raw_buffer_load_b64(rs, voff + (uint32_t)((k0 + 32 * j) * RB), 0, 2));
+  }
   __builtin_amdgcn_sched_barrier(0);
 }
 
@@ -1130,7 +1144,8 @@ __device__ __forceinline__ void row_issue(__amdgpu_buffer_rsrc_t rs, int k0, uin
 // its values from V, merged into the wave's running (M, Lr, A).  Every chunk holds more than 224 keys (the host's
 // row_kernel_fits), so only key group j = 7 can fall past the chunk end.
 constexpr int ROW_JV = 7;
-__device__ __forceinline__ void row_fold(float mw, const float (&sc)[8], const u32x4 (&vr)[8], int k0, int k1, int slot,
+template <typename P>
+__device__ __forceinline__ void row_fold(float mw, const float (&sc)[8], const P (&vr)[8], int k0, int k1, int slot,
                                          float& M, float& Lr, float (&A)[8]) {
   float lw, acc[8], f0 = 0.f, f1 = 0.f;
   wave_values_bf16<32, ROW_JV>(sc, mw, vr, k0, k1, slot, 8, lw, acc);
@@ -1217,6 +1232,102 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
   float m, l, o;
   merge_waves_bf16(stat, red, tid, m, l, o);
   if (tid < HD) TypeIO<bf16_t>::st(p.out + (p.out_t ? kw_tiled_off(b, h * HD + tid, p.out_t) : (int64_t)b * p.d + h * HD + tid), o / l);
+  if constexpr (QG) {
+    if (tid < 32)  // re-arm the row's query for the next launch (every wave of this, its only reader, has read it)
+      __hip_atomic_store(qg + tid, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same pair kernel over the fp8 (e4m3) cross cache (include/kwhisper.h "fp8 cross K/V"): the only grid of
+// kw_cross_attn_step_fp8 / kw_dec_xq_cross_fp8, at every batch size (a row's output then cannot depend on its batch)
+// and for q_len > 1 (one pair per query row and head, each reading its own item's K / V).  Lanes, key slots and
+// arithmetic are cross_attn_row_kernel's, through the same helpers on 8-byte pieces of codes (row_dims decodes them):
+// each wave folds its chunks with row_fold, the four waves merge once with merge_waves_bf16, the query comes from
+// memory or (QG) from the projection workgroups through wait_query_granules.  The pair's 64 K scales multiply the
+// query once, before the first score (8 per lane, loaded with the query), its V scales the output at the final
+// store: no scale is loaded per key.
+// The rotation is the bf16 kernel's too: three sets of 8 pieces (16 registers each here), one chunk in flight while one
+// is computed.  Five sets with two chunks in flight (the registers are there) measured no faster -- 29.2 against 28.9
+// us per launch, profiles/fp8_cross_kbench.txt -- so the bytes in flight do not bound this kernel.
+template <bool QG, int NS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void cross_attn_row_fp8_kernel(CRP8 p) {
+  using P = u32x2;
+  __shared__ __attribute__((aligned(16))) char scratch[QG ? PROJ_SCRATCH : 16];
+  __shared__ float red[4][64];
+  __shared__ float stat[8];
+  if constexpr (QG) {
+    if ((int)blockIdx.x < p.n_lin) {
+      proj_publish_granules<true>(p.proj, blockIdx.x, scratch, p.qg);
+      return;
+    }
+  }
+  const int row = blockIdx.x - (QG ? p.n_lin : 0);
+  const int h = row % p.H, b = row / p.H, item = b / p.q_len;
+  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int sub = lane & 7, slot = wave * 8 + (lane >> 3);
+  const int64_t pair = (int64_t)item * p.H + h;
+  const uint8_t* kb = reinterpret_cast<const uint8_t*>(p.kc) + pair * p.S * HD;
+  const uint8_t* vb = reinterpret_cast<const uint8_t*>(p.vc) + pair * p.S * HD;
+  unsigned long long* qg = QG ? p.qg + (int64_t)b * (p.d / 2) + h * 32 : nullptr;
+  // the query's loads and the lane's 8 K scales first, then the first two chunks' K / V
+  unsigned long long g[4];
+  u32x4 qraw;
+  if constexpr (QG) {
+#pragma unroll
+    for (int i = 0; i < 4; ++i) g[i] = peek_granule(qg + sub * 4 + i);
+  } else {
+    qraw = *reinterpret_cast<const u32x4*>(p.q + (int64_t)b * p.d + h * HD + sub * 8);
+  }
+  const f32x4* ks4 = reinterpret_cast<const f32x4*>(p.ks + pair * HD + sub * 8);
+  const f32x4 ksc[2] = {ks4[0], ks4[1]};
+  constexpr int ns = NS;
+  const int chunk = p.chunk, S = p.S;
+  const __amdgpu_buffer_rsrc_t rsk = __builtin_amdgcn_make_buffer_rsrc((void*)kb, (short)0, S * HD, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc((void*)vb, (short)0, S * HD, 0x00020000);
+  const uint32_t voff = (uint32_t)(slot * HD + sub * 8);
+  P r0[8], r1[8], r2[8];
+  row_issue(rsk, 0, voff, r0);
+  row_issue(rsv, 0, voff, r1);
+  if (ns > 1) row_issue(rsk, chunk, voff, r2);
+  if constexpr (QG) qraw = wait_query_granules(qg + sub * 4, g, p.err);
+  float ql[8];
+  query_log2(qraw, ql);
+#pragma unroll
+  for (int i = 0; i < 8; ++i) ql[i] *= ksc[i >> 2][i & 3];
+  float M = -INFINITY, Lr = 0.f, A[8];
+#pragma unroll
+  for (int i = 0; i < 8; ++i) A[i] = 0.f;
+  // chunk c: K in rk, V in rv (the next chunk's K already in the third set); after the step V(c + 1) is in rk
+  // and K(c + 2) in rv
+  auto step = [&](const int c, P (&rk)[8], P (&rv)[8]) __attribute__((always_inline)) {
+    float sc[8];
+    const int k0 = c * chunk, k1 = min(S, k0 + chunk);
+    const float mw = wave_scores_bf16<32, ROW_JV>(ql, rk, k0, k1, slot, 8, sc);
+    if (c + 1 < ns) row_issue(rsv, k1, voff, rk);
+    row_fold(mw, sc, rv, k0, k1, slot, M, Lr, A);
+    if (c + 2 < ns) row_issue(rsk, k0 + 2 * chunk, voff, rv);
+  };
+#pragma unroll
+  for (int c = 0; c < ns; c += 3) {
+    step(c, r0, r1);                      // K(c) r0, V(c) r1 -> V(c+1) r0, K(c+2) r1
+    if (c + 1 < ns) step(c + 1, r2, r0);  // K(c+1) r2, V(c+1) r0 -> V(c+2) r2, K(c+3) r0
+    if (c + 2 < ns) step(c + 2, r1, r2);  // K(c+2) r1, V(c+2) r2 -> V(c+3) r1, K(c+4) r2
+  }
+  if (lane < 8) {
+#pragma unroll
+    for (int i = 0; i < 8; ++i) red[wave][lane * 8 + i] = A[i];
+  }
+  if (lane == 0) {
+    stat[wave] = M;
+    stat[4 + wave] = Lr;
+  }
+  __syncthreads();
+  float m, l, o;
+  merge_waves_bf16(stat, red, tid, m, l, o);
+  if (tid < HD)
+    TypeIO<bf16_t>::st(p.out + (p.out_t ? kw_tiled_off(b, h * HD + tid, p.out_t) : (int64_t)b * p.d + h * HD + tid),
+                       o * p.vs[pair * HD + tid] / l);
   if constexpr (QG) {
     if (tid < 32)  // re-arm the row's query for the next launch (every wave of this, its only reader, has read it)
       __hip_atomic_store(qg + tid, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1783,13 +1894,16 @@ static bool row_kernel_fits(const CrossGeo& g) {
 
 // the launch descriptor's fields that kw_cross_attn_step and kw_dec_xq_cross fill alike (the query -- a row pointer, or
 // the granules and the projection that publishes them -- is the caller's)
+// (ws null: a launch without hand-offs, kw_cross_attn_step_fp8)
 static CRP cross_crp(const CrossGeo& g, const CrossLayout& L, void* ws, int64_t H, const void* k, const void* v, void* out) {
   CRP p{};
-  p.gran = L.at<unsigned long long>(ws, L.wave_gran);
+  if (ws) {
+    p.gran = L.at<unsigned long long>(ws, L.wave_gran);
+    p.err = L.at<int>(ws, L.status);
+  }
   p.kc = (const bf16_t*)k;
   p.vc = (const bf16_t*)v;
   p.H = (int)H, p.d = (int)(H * HD), p.S = (int)g.S, p.chunk = g.chunk, p.ns = g.ns;
-  p.err = L.at<int>(ws, L.status);
   p.out = (bf16_t*)out;
   return p;
 }
@@ -1892,6 +2006,72 @@ extern "C" int kw_dec_xq_cross(const kw_dec_xq_cross_args* a, kw_stream_t stream
                        (hipStream_t)stream, p);
   else  // the chunk grid
     hipLaunchKernelGGL(xq_cross_kernel, dim3((unsigned)(p.n_lin + g.rows * g.ns)), dim3(256), 0, (hipStream_t)stream, p);
+  KW_CHECK_LAUNCH();
+  return KW_OK;
+}
+
+// ---- the fp8 (e4m3) cross cache ------------------------------------------------------------------------------
+
+// the one grid of the fp8 path: S must give the pair kernel its six chunks, each reaching key group ROW_JV
+// the fp8 kernels' descriptor: cross_crp's fields over the codes, the layer's scales, q_len query rows per item
+static CRP8 cross_crp8(const CRP& base, const float* ks, const float* vs, int64_t q_len) {
+  CRP8 p{};
+  static_cast<CRP&>(p) = base;
+  p.ks = ks, p.vs = vs, p.q_len = (int)q_len;
+  return p;
+}
+
+static bool fp8_geo_ok(const CrossGeo& g) { return g.S <= 2048 && g.ns == ROW_NS && g.row_groups_ok(); }
+#define FP8_GEO_MSG ": S must split into 6 chunks of 225..256 keys (e.g. 1500, 1399, 1536)"
+
+extern "C" int kw_cross_attn_step_fp8(const void* q, int64_t B, int64_t q_len, int64_t H, int64_t hd, const void* k,
+                                      const void* v, const float* k_scale, const float* v_scale, int64_t S, void* out,
+                                      kw_stream_t stream) {
+  if (!q || !k || !v || !k_scale || !v_scale || !out || B <= 0 || q_len <= 0 || H <= 0 || S <= 0)
+    return kw_set_error_msg(KW_EINVAL, "kw_cross_attn_step_fp8: invalid arguments");
+  if (hd != HD) return kw_set_error_msg(KW_EUNSUPPORTED, "kw_cross_attn_step_fp8: head_dim must be 64");
+  const CrossGeo g(B * q_len * H, S);
+  if (!fp8_geo_ok(g))
+    return kw_set_error_msg(KW_EUNSUPPORTED, "kw_cross_attn_step_fp8" FP8_GEO_MSG);
+  if (g.rows > 0x7fffffff || (uintptr_t)q % 16 || (uintptr_t)k % 16 || (uintptr_t)v % 16 || (uintptr_t)k_scale % 16)
+    return kw_set_error_msg(KW_EINVAL, "kw_cross_attn_step_fp8: q, k, v and k_scale must be 16-B aligned");
+  CRP8 p = cross_crp8(cross_crp(g, CrossLayout(g), nullptr, H, k, v, out), k_scale, v_scale, q_len);
+  p.q = (const bf16_t*)q;
+  hipLaunchKernelGGL((cross_attn_row_fp8_kernel<false, ROW_NS>), dim3((unsigned)g.rows), dim3(256), 0, (hipStream_t)stream, p);
+  KW_CHECK_LAUNCH();
+  return KW_OK;
+}
+
+static bool xq_fp8_shape_ok(int64_t M, int64_t d, int64_t H, int64_t S) {
+  return proj_shape_ok(M, d) && H >= 1 && d == HD * H && S >= 1 && fp8_geo_ok(CrossGeo(M * H, S));
+}
+
+extern "C" int kw_dec_xq_cross_fp8_supported(int64_t M, int64_t d, int64_t H, int64_t S) {
+  return xq_fp8_shape_ok(M, d, H, S) ? 1 : 0;  // (every wait is on earlier-dispatched work: no residency condition)
+}
+
+extern "C" int kw_dec_xq_cross_fp8(const kw_dec_xq_cross_fp8_args* a, kw_stream_t stream) {
+  if (!a || !a->x || !a->W || !a->ln_colsum || !a->k || !a->v || !a->k_scale || !a->v_scale || !a->out || !a->workspace)
+    return kw_set_error_msg(KW_EINVAL, "kw_dec_xq_cross_fp8: null pointer");
+  if (a->M >= 1 && a->H >= 1 && a->S >= 1 && proj_shape_ok(a->M, a->d) && a->d == HD * a->H && !fp8_geo_ok(CrossGeo(a->M * a->H, a->S)))
+    return kw_set_error_msg(KW_EUNSUPPORTED, "kw_dec_xq_cross_fp8" FP8_GEO_MSG);
+  if (!xq_fp8_shape_ok(a->M, a->d, a->H, a->S) || (a->ldx != KW_LD_TILED && (a->ldx < a->d || a->ldx % 8)) ||
+      (uintptr_t)a->x % 16 || (uintptr_t)a->k % 16 || (uintptr_t)a->v % 16 || (uintptr_t)a->k_scale % 16)
+    return kw_set_error_msg(KW_EINVAL, "kw_dec_xq_cross_fp8: M <= 32 rows, d = 64 H <= 1280, ldx % 8 == 0, 16-B aligned x, "
+                                       "k, v and k_scale");
+  const CrossGeo g(a->M * a->H, a->S);
+  const CrossLayout L(g, a->M * (a->d / 2));
+  if (a->ws_bytes < L.fused_end)
+    return kw_set_error_msg(KW_EINVAL, "kw_dec_xq_cross_fp8: needs a zero-filled workspace of kw_dec_xq_cross_workspace()");
+  CRP8 p = cross_crp8(cross_crp(g, L, a->workspace, a->H, a->k, a->v, a->out), a->k_scale, a->v_scale, 1);
+  const int M = (int)a->M, d = (int)a->d;
+  p.qg = L.at<unsigned long long>(a->workspace, L.query_gran);
+  p.n_lin = d / 16;
+  p.out_t = a->ldx == KW_LD_TILED ? (M + 15) / 16 : 0;
+  p.proj = ProjArgs{reinterpret_cast<const bf16_t*>(a->x), a->ldx, M, d, d, a->ln_eps, a->ln_colsum,
+                    reinterpret_cast<const bf16x8*>(a->W), a->bias, a->scale, d, p.err + 1};
+  hipLaunchKernelGGL((cross_attn_row_fp8_kernel<true, ROW_NS>), dim3((unsigned)(p.n_lin + g.rows)), dim3(256), 0,
+                     (hipStream_t)stream, p);
   KW_CHECK_LAUNCH();
   return KW_OK;
 }

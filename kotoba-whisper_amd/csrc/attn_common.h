@@ -47,8 +47,25 @@ __device__ __forceinline__ void query_log2(const u32x4& qraw, float ql[8]) {
   for (int i = 0; i < 8; ++i) ql[i] *= LOG2E;
 }
 
+// a lane's 8 dims of one key / value row as f32, from the piece the kernel holds them in: 16 B of bf16 (u32x4), or 8 B
+// of e4m3 codes (u32x2: the fp8 cross cache, whose per-dim scales the caller folds into the query and the output)
+__device__ __forceinline__ void row_dims(const u32x4& r, float v[8]) {
+#pragma unroll
+  for (int i = 0; i < 4; ++i) {
+    v[2 * i] = __uint_as_float(r[i] << 16);
+    v[2 * i + 1] = __uint_as_float(r[i] & 0xffff0000u);
+  }
+}
+__device__ __forceinline__ void row_dims(const u32x2& r, float v[8]) {
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const auto lo = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[i], false), hi = __builtin_amdgcn_cvt_pk_f32_fp8((int)r[i], true);
+    v[4 * i] = lo[0], v[4 * i + 1] = lo[1], v[4 * i + 2] = hi[0], v[4 * i + 3] = hi[1];
+  }
+}
+
 // bf16 decode attention, one query row over one wave's key groups j (lane (slot, sub) holds 16 B of key rows
-// slot + 32 j): scores in log2 units (the query carries log2 e, so p = exp2(s - m) is one v_exp), the wave's
+// slot + 32 j -- or their 8 B of e4m3 codes, row_dims): scores in log2 units (the query carries log2 e, so p = exp2(s - m) is one v_exp), the wave's
 // OWN softmax reference m_w (no workgroup barrier between the scores and the values), the row sum and the 8
 // value dims of this lane reduced over the wave's key slots.  The workgroup merges its waves' (m_w, l_w, o_w)
 // once at the end (merge_waves_bf16), and chunks merge with exp2 of log2-unit maxima.  Every multiply-add is
@@ -57,20 +74,27 @@ __device__ __forceinline__ void query_log2(const u32x4& qraw, float ql[8]) {
 // and the wave maximum ...
 // JV: the first key group j that can fall past the chunk end (a caller whose chunks all hold more than KS * (JV - 1)
 // keys passes JV > 0 and the groups below it skip the check; the arithmetic is the same)
-template <int KS = 32, int JV = 0>  // key of (slot, j) = k0 + slot + KS * j (32 key slots per 4-wave row, 16 per 2-wave row)
-__device__ __forceinline__ float wave_scores_bf16(const float ql[8], const u32x4 kr[8], int k0, int k1, int slot,
+template <int KS = 32, int JV = 0, typename P = u32x4>  // key of (slot, j) = k0 + slot + KS * j (32 key slots per 4-wave row, 16 per 2-wave row)
+__device__ __forceinline__ float wave_scores_bf16(const float ql[8], const P kr[8], int k0, int k1, int slot,
                                                   int nj, float sc[8]) {
   float mx = -INFINITY;
 #pragma unroll
   for (int j = 0; j < 8; ++j) {
     sc[j] = -INFINITY;
     if (j < nj) {
-      const uint32_t w[4] = {kr[j][0], kr[j][1], kr[j][2], kr[j][3]};
       float sj = 0.f;
+      if constexpr (sizeof(P) == 16) {
+        const uint32_t w[4] = {kr[j][0], kr[j][1], kr[j][2], kr[j][3]};
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        sj = fmaf(ql[2 * i], __uint_as_float(w[i] << 16), sj);
-        sj = fmaf(ql[2 * i + 1], __uint_as_float(w[i] & 0xffff0000u), sj);
+        for (int i = 0; i < 4; ++i) {
+          sj = fmaf(ql[2 * i], __uint_as_float(w[i] << 16), sj);
+          sj = fmaf(ql[2 * i + 1], __uint_as_float(w[i] & 0xffff0000u), sj);
+        }
+      } else {
+        float kf[8];
+        row_dims(kr[j], kf);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) sj = fmaf(ql[i], kf[i], sj);
       }
       sj = kw_sum8(sj);
       sc[j] = (j < JV || k0 + slot + KS * j < k1) ? sj : -INFINITY;
@@ -81,8 +105,8 @@ __device__ __forceinline__ float wave_scores_bf16(const float ql[8], const u32x4
 }
 
 // ... then p = exp2(s - m_w), the row sum and this lane's 8 value dims reduced over the wave's key slots
-template <int KS = 32, int JV = 0>
-__device__ __forceinline__ void wave_values_bf16(const float sc[8], float mx, const u32x4 vr[8], int k0, int k1,
+template <int KS = 32, int JV = 0, typename P = u32x4>
+__device__ __forceinline__ void wave_values_bf16(const float sc[8], float mx, const P vr[8], int k0, int k1,
                                                  int slot, int nj, float& lw, float acc[8]) {
   float lsum = 0.f;
 #pragma unroll
@@ -95,12 +119,20 @@ __device__ __forceinline__ void wave_values_bf16(const float sc[8], float mx, co
       lsum += pj;
       // a masked slot holds a clamped row that may be STALE (a cache row this step has not written yet, e.g. the
       // new position's row before its append): p = 0 times a stale NaN / Inf is NaN, so its values are zeroed
-      const uint32_t w[4] = {valid ? vr[j][0] : 0u, valid ? vr[j][1] : 0u, valid ? vr[j][2] : 0u,
-                             valid ? vr[j][3] : 0u};
+      if constexpr (sizeof(P) == 16) {
+        const uint32_t w[4] = {valid ? vr[j][0] : 0u, valid ? vr[j][1] : 0u, valid ? vr[j][2] : 0u,
+                               valid ? vr[j][3] : 0u};
 #pragma unroll
-      for (int i = 0; i < 4; ++i) {
-        acc[2 * i] = fmaf(pj, __uint_as_float(w[i] << 16), acc[2 * i]);
-        acc[2 * i + 1] = fmaf(pj, __uint_as_float(w[i] & 0xffff0000u), acc[2 * i + 1]);
+        for (int i = 0; i < 4; ++i) {
+          acc[2 * i] = fmaf(pj, __uint_as_float(w[i] << 16), acc[2 * i]);
+          acc[2 * i + 1] = fmaf(pj, __uint_as_float(w[i] & 0xffff0000u), acc[2 * i + 1]);
+        }
+      } else {
+        const P w = {valid ? vr[j][0] : 0u, valid ? vr[j][1] : 0u};
+        float vf[8];
+        row_dims(w, vf);
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] = fmaf(pj, vf[i], acc[i]);
       }
     }
   }

@@ -247,6 +247,64 @@ void dec_xq_cross(const Tensor& x, const Tensor& W, const optional<Tensor>& bias
   check(kw_dec_xq_cross(&a, stream_of(x)), w);
 }
 
+// ---- fp8 cross K/V: quantisation, step, fused query + step ------------------------------------------------
+void cross_kv_quant(const Tensor& x, int64_t n, int64_t S, int64_t hd, Tensor& codes, Tensor& scales) {
+  const char* w = "kw_cross_kv_quant";
+  dev(x, w), dev(codes, w), dev(scales, w);
+  TORCH_CHECK_VALUE(x.scalar_type() == at::kBFloat16 && codes.scalar_type() == at::kByte && scales.scalar_type() == at::kFloat &&
+                        x.numel() >= n * S * hd && codes.numel() >= n * S * hd && scales.numel() >= n * hd,
+                    "kw_cross_kv_quant: x bf16 [n][S][hd], codes uint8 [n][S][hd], scales f32 [n][hd]");
+  c10::DeviceGuard g(x.device());
+  check(kw_cross_kv_quant(ptr(x), n, S, hd, ptr(codes), ptr<float>(scales), stream_of(x)), w);
+}
+
+void cross_attn_step_fp8(const Tensor& q, int64_t B, int64_t q_len, int64_t H, int64_t hd, const Tensor& k, const Tensor& v,
+                         const Tensor& k_scale, const Tensor& v_scale, int64_t S, Tensor& out) {
+  const char* w = "kw_cross_attn_step_fp8";
+  dev(q, w), dev(k, w), dev(v, w), dev(k_scale, w), dev(v_scale, w), dev(out, w);
+  TORCH_CHECK_VALUE(q.scalar_type() == at::kBFloat16 && out.scalar_type() == at::kBFloat16 && k.scalar_type() == at::kByte &&
+                        v.scalar_type() == at::kByte && k_scale.scalar_type() == at::kFloat && v_scale.scalar_type() == at::kFloat,
+                    "kw_cross_attn_step_fp8 takes a bf16 query and output, uint8 (e4m3) K / V and f32 scales");
+  c10::DeviceGuard g(q.device());
+  check(kw_cross_attn_step_fp8(ptr(q), B, q_len, H, hd, ptr(k), ptr(v), ptr<const float>(k_scale), ptr<const float>(v_scale), S,
+                               ptr(out), stream_of(q)),
+        w);
+}
+
+// dims = [ldx, M, d, H, S]
+void dec_xq_cross_fp8(const Tensor& x, const Tensor& W, const optional<Tensor>& bias, const Tensor& ln_colsum,
+                      const Tensor& k, const Tensor& v, const Tensor& k_scale, const Tensor& v_scale, Tensor& out,
+                      Tensor& workspace, std::vector<int64_t> dims, double ln_eps, double scale) {
+  const char* w = "kw_dec_xq_cross_fp8";
+  dev(x, w), dev(W, w), dev(bias, w), dev(ln_colsum, w), dev(k, w), dev(v, w), dev(k_scale, w), dev(v_scale, w), dev(out, w),
+      dev(workspace, w);
+  TORCH_CHECK_VALUE(dims.size() == 5, "kw_dec_xq_cross_fp8: dims must hold 5 integers");
+  TORCH_CHECK_VALUE(x.scalar_type() == at::kBFloat16 && W.scalar_type() == at::kBFloat16 &&
+                        out.scalar_type() == at::kBFloat16 && k.scalar_type() == at::kByte && v.scalar_type() == at::kByte &&
+                        k_scale.scalar_type() == at::kFloat && v_scale.scalar_type() == at::kFloat,
+                    "kw_dec_xq_cross_fp8 takes bf16 activations, packed bf16 weights, uint8 (e4m3) K / V, f32 scales and "
+                    "a bf16 output");
+  kw_dec_xq_cross_fp8_args a{};
+  a.x = ptr(x);
+  a.ldx = dims[0];
+  a.ln_eps = (float)ln_eps;
+  a.ln_colsum = ptr<const float>(ln_colsum);
+  a.W = ptr(W);
+  a.bias = optr<const float>(bias);
+  a.scale = (float)scale;
+  a.M = dims[1], a.d = dims[2], a.H = dims[3];
+  a.k = ptr(k);
+  a.v = ptr(v);
+  a.k_scale = ptr<const float>(k_scale);
+  a.v_scale = ptr<const float>(v_scale);
+  a.S = dims[4];
+  a.out = ptr(out);
+  a.workspace = ptr(workspace);
+  a.ws_bytes = (size_t)workspace.numel() * workspace.element_size();
+  c10::DeviceGuard g(x.device());
+  check(kw_dec_xq_cross_fp8(&a, stream_of(x)), w);
+}
+
 // ---- fused decode self-attention block (LayerNorm-fused QKV projection + self-attention step) ------------
 // dims = [ldx, M, d, H, t_max]
 void dec_qkv_self(const Tensor& x, const Tensor& W, const optional<Tensor>& bias, const Tensor& ln_colsum,
@@ -605,6 +663,11 @@ TORCH_LIBRARY(kw, m) {
         "Tensor cur_len, Tensor(c!) out, Tensor(d!) workspace, int[] dims, float ln_eps, float scale) -> ()");
   m.def("dec_xq_cross(Tensor x, Tensor W, Tensor? bias, Tensor ln_colsum, Tensor k, Tensor v, Tensor(a!) out, "
         "Tensor(b!) workspace, int[] dims, float ln_eps, float scale) -> ()");
+  m.def("cross_kv_quant(Tensor x, int n, int S, int hd, Tensor(a!) codes, Tensor(b!) scales) -> ()");
+  m.def("cross_attn_step_fp8(Tensor q, int B, int q_len, int H, int hd, Tensor k, Tensor v, Tensor k_scale, Tensor v_scale, "
+        "int S, Tensor(a!) out) -> ()");
+  m.def("dec_xq_cross_fp8(Tensor x, Tensor W, Tensor? bias, Tensor ln_colsum, Tensor k, Tensor v, Tensor k_scale, "
+        "Tensor v_scale, Tensor(a!) out, Tensor(b!) workspace, int[] dims, float ln_eps, float scale) -> ()");
   m.def("cross_attn_step(Tensor q, int B, int q_len, int H, int hd, Tensor k, Tensor v, int S, Tensor(a!) out, "
         "Tensor(b!) workspace) -> ()");
   m.def("greedy_step(Tensor(a!) logits, Tensor suppress_mask, Tensor? begin_suppress, Tensor(b!) ids, "
@@ -643,6 +706,9 @@ TORCH_LIBRARY_IMPL(kw, CUDA, m) {
   m.impl("cross_attn_step", &cross_attn_step);
   m.impl("dec_qkv_self", &dec_qkv_self);
   m.impl("dec_xq_cross", &dec_xq_cross);
+  m.impl("cross_kv_quant", &cross_kv_quant);
+  m.impl("cross_attn_step_fp8", &cross_attn_step_fp8);
+  m.impl("dec_xq_cross_fp8", &dec_xq_cross_fp8);
   m.impl("greedy_step", &greedy_step);
   m.impl("sample_step", &sample_step);
   m.impl("dec_lm_greedy", &dec_lm_greedy);

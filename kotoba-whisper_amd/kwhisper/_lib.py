@@ -21,7 +21,8 @@ TORCH_LIB_PATH = os.environ.get("KWHISPER_TORCH_LIB") or os.path.join(os.path.di
                                                                       "libkwhisper_torch.so")
 TORCH_OPS = ("log_mel", "mel_to_time_major", "gemm", "dec_linear", "pack_weight", "layernorm", "attention", "embed",
              "self_attn_step", "dec_qkv_self", "dec_xq_cross", "cross_attn_step", "greedy_step", "sample_step", "dec_lm_greedy",
-             "beam_logprobs", "beam_select", "align_capture", "align_weights", "align_reduce", "dtw")
+             "beam_logprobs", "beam_select", "align_capture", "align_weights", "align_reduce", "dtw", "cross_kv_quant",
+             "cross_attn_step_fp8", "dec_xq_cross_fp8")
 
 KW_OK, KW_EINVAL, KW_EHIP, KW_EUNSUPPORTED = 0, 1, 2, 3
 KW_DT_F32, KW_DT_BF16 = 0, 1
@@ -71,6 +72,15 @@ class XqCrossArgs(ctypes.Structure):
         ("x", c_vp), ("ldx", c_i64), ("ln_eps", ctypes.c_float), ("ln_colsum", c_vp), ("W", c_vp), ("bias", c_vp),
         ("scale", ctypes.c_float), ("M", c_i64), ("d", c_i64), ("H", c_i64), ("k", c_vp), ("v", c_vp),
         ("S", c_i64), ("out", c_vp), ("workspace", c_vp), ("ws_bytes", ctypes.c_size_t),
+    ]
+
+
+class XqCrossFp8Args(ctypes.Structure):
+    _fields_ = [
+        ("x", c_vp), ("ldx", c_i64), ("ln_eps", ctypes.c_float), ("ln_colsum", c_vp), ("W", c_vp), ("bias", c_vp),
+        ("scale", ctypes.c_float), ("M", c_i64), ("d", c_i64), ("H", c_i64), ("k", c_vp), ("v", c_vp),
+        ("k_scale", c_vp), ("v_scale", c_vp), ("S", c_i64), ("out", c_vp), ("workspace", c_vp),
+        ("ws_bytes", ctypes.c_size_t),
     ]
 
 
@@ -156,6 +166,10 @@ EXPORTS = {
     "kw_dec_xq_cross_workspace": (ctypes.c_size_t, [c_i64, c_i64, c_i64, c_i64]),
     "kw_dec_xq_cross_supported": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64]),
     "kw_cross_attn_pair_kernel": (ctypes.c_int, [c_i64, c_i64, ctypes.c_int]),
+    "kw_cross_kv_quant": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp]),
+    "kw_cross_attn_step_fp8": (ctypes.c_int, [c_vp, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "kw_dec_xq_cross_fp8": (ctypes.c_int, [ctypes.POINTER(XqCrossFp8Args), c_vp]),
+    "kw_dec_xq_cross_fp8_supported": (ctypes.c_int, [c_i64, c_i64, c_i64, c_i64]),
     "kw_dec_qkv_self_status_offset": (ctypes.c_size_t, [c_i64, c_i64]),
     "kw_dec_xq_cross_status_offset": (ctypes.c_size_t, [c_i64, c_i64, c_i64, c_i64]),
     "kw_cross_attn_status_offset": (ctypes.c_size_t, [c_i64, c_i64, c_i64, c_i64, c_i64]),

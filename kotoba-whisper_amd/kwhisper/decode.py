@@ -60,7 +60,13 @@ class DecodeSession:
         dev, dt = eng.device, eng.dtype
         d, H, Ld = s.d_model, eng.H, s.decoder_layers
         self.T = s.max_source_positions
-        self.cross = torch.empty((2 * Ld, B, H, self.T, _HD), device=dev, dtype=dt)
+        # fp8 cross K/V (WhisperEngine(cross_kv_dtype="fp8_e4m3")): e4m3 codes in the bf16 cache's layout and one f32
+        # scale per (K/V of a layer, item, head, head dim) instead of the bf16 cache; greedy rows only
+        self.fp8 = bool(getattr(eng, "cross_kv_fp8", False))
+        if self.fp8 and beams > 1:
+            raise NotImplementedError("beam search is not supported with cross_kv_dtype='fp8_e4m3'")
+        self.cross = torch.empty((2 * Ld, B, H, self.T, _HD), device=dev, dtype=torch.uint8 if self.fp8 else dt)
+        self.cross_scale = torch.empty((2 * Ld, B, H, _HD), device=dev, dtype=torch.float32) if self.fp8 else None
         self.kc = torch.zeros((Ld, R, H, T_MAX, _HD), device=dev, dtype=dt)
         self.vc = torch.zeros((Ld, R, H, T_MAX, _HD), device=dev, dtype=dt)
         self.ids = torch.zeros((R, T_MAX + 1), device=dev, dtype=torch.int64)
@@ -94,8 +100,9 @@ class DecodeSession:
                                  dtype=torch.float32) if self.qs_ok else None
         self.fused_last = False  # whether the last step plan built / replayed used kw_dec_qkv_self
         # fused cross-attention query + step (kw_dec_xq_cross): one query row per item (greedy), any position
+        # (over the fp8 cache: kw_dec_xq_cross_fp8, the same workspace and status words)
         self.xc_ok = (eng.packed and beams == 1 and eng.fuse_xq_cross and R <= 32
-                      and ops.xq_cross_supported(R, d, H, self.T))
+                      and (ops.xq_cross_fp8_supported if self.fp8 else ops.xq_cross_supported)(R, d, H, self.T))
         self.xc_ws = torch.zeros(((ops.xq_cross_workspace_bytes(R, d, H, self.T) + 3) // 4,), device=dev,
                                  dtype=torch.float32) if self.xc_ok else None
         # fragment-major bf16 residual mirror (KW_LD_TILED) for the q = 1 step: the kernels that read hb there (the
@@ -127,7 +134,7 @@ class DecodeSession:
         decodes several prompts against one encoder pass, run_pseudo_labelling_v3.py:309-321)."""
         if key is not None and key == self._cross_key:
             return
-        self.eng.cross_kv(enc, self.B, out=self.cross)
+        self.eng.cross_kv(enc, self.B, out=(self.cross, self.cross_scale) if self.fp8 else self.cross)
         self._cross_key = key
 
     def _row_view(self, r0: int, r1: int) -> "DecodeSession":
@@ -138,6 +145,7 @@ class DecodeSession:
         v = object.__new__(DecodeSession)
         v.eng, v.nb, v.B, v.R, v.T = self.eng, 1, r1 - r0, r1 - r0, self.T
         v.cross, v.kc, v.vc = self.cross[:, r0:r1], self.kc[:, r0:r1], self.vc[:, r0:r1]
+        v.fp8, v.cross_scale = self.fp8, self.cross_scale[:, r0:r1] if self.fp8 else None
         v.ids, v.bp, v.cur_len, v.logits = self.ids[r0:r1], None, self.cur_len, self.logits[r0:r1]
         v._bufs, v._plans, v._align_logs = {}, {}, {}
         v.lin_ws = torch.zeros_like(self.lin_ws) if self.lin_ws is not None else None
@@ -192,9 +200,11 @@ class DecodeSession:
                 torch.empty((rows, d), device=dev, dtype=dt),
                 qx=torch.empty((rows, d), device=dev, dtype=dt),
                 ffn=torch.empty((rows, s.decoder_ffn_dim), device=dev, dtype=dt),
-                # cross-attention partials + arrival counters (must start zeroed; kernels leave them zeroed)
-                ws=torch.zeros((ops.cross_attn_workspace_bytes(self.B, q * self.nb, self.eng.H, _HD, self.T) // 4 + 1,),
-                               device=dev, dtype=torch.float32),
+                # cross-attention partials + arrival counters (must start zeroed; kernels leave them zeroed); the fp8
+                # cross-attention takes no workspace
+                ws=None if self.fp8 else
+                torch.zeros((ops.cross_attn_workspace_bytes(self.B, q * self.nb, self.eng.H, _HD, self.T) // 4 + 1,),
+                            device=dev, dtype=torch.float32),
             )
             if self.eng.packed:  # bf16 mirror of the residual stream (the LayerNorm-fused linears' operand)
                 if q == 1 and self.tiled_ok:  # fragment-major: whole 16-row tiles, rows >= R zero and never written
@@ -262,7 +272,12 @@ class DecodeSession:
                 seq.append(lin(b["attn"], lay["o_w"], rows, d, d, bias=lay["o_b"], resid=(h, hb, d, 0), workspace=ws,
                                tag="o", hb_tiled=tiled, ldx=xld if fused else None))  # (the fused block's attn)
                 xc = q == 1 and self.xc_ok and li not in capture
-                if xc:
+                if xc and self.fp8:
+                    seq.append(ops.XqCrossFp8Plan(hb, lay["xq_w"], rows, d, H, ln=(eps, lay["xq_cs"]), bias=lay["xq_b"],
+                                                  scale=scale, k=self.cross[2 * li], v=self.cross[2 * li + 1],
+                                                  k_scale=self.cross_scale[2 * li], v_scale=self.cross_scale[2 * li + 1],
+                                                  S=self.T, out=b["attn"], workspace=self.xc_ws, ldx=xld))
+                elif xc:
                     seq.append(ops.XqCrossPlan(hb, lay["xq_w"], rows, d, H, ln=(eps, lay["xq_cs"]), bias=lay["xq_b"],
                                                scale=scale, k=self.cross[2 * li], v=self.cross[2 * li + 1], S=self.T,
                                                out=b["attn"], workspace=self.xc_ws, ldx=xld))
@@ -326,8 +341,12 @@ class DecodeSession:
                                    bp=self.bp if q == 1 else None)
             elif k == "cross":  # rows b*nb*q + (beam*q + i) attend to item b's K/V
                 _, q, qx, li, out, ws = p
-                ops.cross_attn_step(qx, self.B, q * self.nb, H, _HD, self.cross[2 * li], self.cross[2 * li + 1],
-                                    self.T, out, ws)
+                if self.fp8:
+                    ops.cross_attn_step_fp8(qx, self.B, q * self.nb, H, _HD, self.cross[2 * li], self.cross[2 * li + 1],
+                                            self.cross_scale[2 * li], self.cross_scale[2 * li + 1], self.T, out)
+                else:
+                    ops.cross_attn_step(qx, self.B, q * self.nb, H, _HD, self.cross[2 * li], self.cross[2 * li + 1],
+                                        self.T, out, ws)
 
     # ------------------------------------------------------------------------------------------
     def status_words(self):
@@ -339,10 +358,12 @@ class DecodeSession:
         if self.qs_ws is not None:
             out.append(("kw_dec_qkv_self", self.qs_ws, ops.status_offset("qkv_self", self.R, s.d_model)))
         if self.xc_ws is not None:
-            out.append(("kw_dec_xq_cross", self.xc_ws, ops.status_offset("xq_cross", self.R, s.d_model, H, self.T)))
+            out.append(("kw_dec_xq_cross_fp8" if self.fp8 else "kw_dec_xq_cross", self.xc_ws,
+                        ops.status_offset("xq_cross", self.R, s.d_model, H, self.T)))
         for q, b in self._bufs.items():
-            out.append(("kw_cross_attn_step", b["ws"], ops.status_offset("cross_attn", self.B, q * self.nb, H, _HD,
-                                                                         self.T)))
+            if b["ws"] is not None:  # (kw_cross_attn_step_fp8 has no hand-off)
+                out.append(("kw_cross_attn_step", b["ws"], ops.status_offset("cross_attn", self.B, q * self.nb, H, _HD,
+                                                                             self.T)))
         return out
 
     def check_handoffs(self) -> None:
@@ -437,6 +458,9 @@ class DecodeSession:
                 raise ValueError(f"alignment_heads must be [layer, head] pairs within {nl} layers x {nh} heads")
             if self.nb != 1:
                 raise NotImplementedError("token timestamps with beam search")
+            if self.fp8:
+                raise NotImplementedError("token timestamps with cross_kv_dtype='fp8_e4m3' (kw_align_weights reads the "
+                                          "bf16 K cache)")
         self.align_out = None
         B = self.B
         P = prompt.shape[1]
@@ -473,7 +497,7 @@ class DecodeSession:
         key = (max_length, P, bool(return_timestamps), tuple(gen.suppress_tokens or ()),
                tuple(gen.begin_suppress_tokens or ()), gen.timestamp_begin, gen.no_timestamps_token_id,
                gen.eos_token_id, gen.pad_token_id, gen.max_initial_timestamp_index, bool(record_scores),
-               self.eng.prefill_streams, self.eng.fuse_lm_greedy, align)
+               self.eng.prefill_streams, self.eng.fuse_lm_greedy, align, "fp8_e4m3" if self.fp8 else None)
         if sample is not None:
             key += ("sample",)
         cfg = self._greedy_cfg.get(key)

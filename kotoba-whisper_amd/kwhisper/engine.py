@@ -64,9 +64,20 @@ class WhisperEngine:
     def __init__(self, shape: WhisperShape, state_dict: dict, *, dtype=torch.bfloat16, device="cuda",
                  generation_config: GenerationConstants | None = None, fuse_qkv_self: bool = True,
                  fuse_xq_cross: bool = True, encoder_streams: int = 2, prefill_streams: int = 2,
-                 steps_per_replay: int = 2, fuse_lm_greedy: bool = True, tiled_act: bool = True):
+                 steps_per_replay: int = 2, fuse_lm_greedy: bool = True, tiled_act: bool = True,
+                 cross_kv_dtype: str | None = None):
         if dtype not in (torch.bfloat16, torch.float32):
             raise ValueError("dtype must be torch.bfloat16 or torch.float32")
+        # the cross-attention K/V cache: None / "bf16" keeps it in the compute dtype (the reference's arithmetic, the
+        # default); "fp8_e4m3" (bf16 engine only) holds it as OCP e4m3 codes with one f32 scale per (K/V of a layer,
+        # item, head, head dim) -- include/kwhisper.h "fp8 cross K/V", DESIGN.md §6c: half the bytes the decode step
+        # streams and half the resident cache, outside the bf16 parity bar.  Greedy decoding only.
+        if cross_kv_dtype not in (None, "bf16", "fp8_e4m3"):
+            raise ValueError(f"cross_kv_dtype must be None, 'bf16' or 'fp8_e4m3', not {cross_kv_dtype!r}")
+        if cross_kv_dtype == "fp8_e4m3" and dtype != torch.bfloat16:
+            raise ValueError("cross_kv_dtype='fp8_e4m3' needs dtype=torch.bfloat16 (the packed-weight decode path)")
+        self.cross_kv_dtype = cross_kv_dtype
+        self.cross_kv_fp8 = cross_kv_dtype == "fp8_e4m3"
         L.load()
         L.load_torch_ops()  # torch.ops.kw.* (the launch path of every op); raises if it was not built
         self.shape = shape
@@ -109,6 +120,7 @@ class WhisperEngine:
         self._enc = {}
         self._enc_split = {}
         self._enc_streams = []
+        self._kv_stage = {}  # fp8 cross K/V: the bf16 staging buffer of one layer group, per batch size
 
     # ------------------------------------------------------------------------------------------
     def _dev(self, t: torch.Tensor, dtype=None) -> torch.Tensor:
@@ -325,10 +337,35 @@ class WhisperEngine:
         return out
 
     # ------------------------------------------------------------------------------------------
-    def cross_kv(self, enc: torch.Tensor, B: int, out: torch.Tensor | None = None) -> torch.Tensor:
-        """All decoder layers' cross-attention K/V in one GEMM: [2L][B][H][1500][64] (modeling_whisper.py:323-335)."""
+    # fp8 cross K/V: decoder layers projected and quantised per group.  4 layers: the staging buffer is 1/8 of the bf16
+    # cache at large-v3 (0.98 GB at B = 32, beside the 3.93 GB of codes -- not 7.86 + 3.93), while each group's GEMM
+    # still has 8 x d output columns (80 column tiles of 128 at large-v3), enough to fill the device as the one GEMM does
+    KV_GROUP_LAYERS = 4
+
+    def cross_kv(self, enc: torch.Tensor, B: int, out=None):
+        """All decoder layers' cross-attention K/V: [2L][B][H][1500][64] in one GEMM (modeling_whisper.py:323-335).
+        With ``cross_kv_dtype="fp8_e4m3"``: (codes uint8 [2L][B][H][1500][64], scales f32 [2L][B][H][64]), projected by
+        groups of ``KV_GROUP_LAYERS`` layers into an engine-owned bf16 staging buffer (the same GEMM over a row slice
+        of the weights) and quantised from there (kw_cross_kv_quant); ``out`` is then that pair."""
         s = self.shape
         T, d = s.max_source_positions, s.d_model
+        if self.cross_kv_fp8:
+            Ld, G = s.decoder_layers, min(self.KV_GROUP_LAYERS, s.decoder_layers)
+            if out is None:
+                out = (torch.empty((2 * Ld, B, self.H, T, _HD), device=self.device, dtype=torch.uint8),
+                       torch.empty((2 * Ld, B, self.H, _HD), device=self.device, dtype=torch.float32))
+            codes, scales = out
+            stage = self._kv_stage.get(B)
+            if stage is None:
+                stage = self._kv_stage[B] = torch.empty((2 * G, B, self.H, T, _HD), device=self.device, dtype=self.dtype)
+            for l0 in range(0, Ld, G):
+                g = min(G, Ld - l0)
+                r0, r1 = 2 * l0, 2 * (l0 + g)
+                ops.GemmPlan(enc, self.cross_kv_w[r0 * d:r1 * d], stage, B * T, (r1 - r0) * d, d,
+                             bias=self.cross_kv_b[r0 * d:r1 * d], epilogue=L.KW_EPI_HEADSPLIT, hs_seq=T, hs_heads=self.H,
+                             hs_head_dim=_HD)()
+                ops.cross_kv_quant(stage[:r1 - r0], codes[r0:r1], scales[r0:r1])
+            return out
         n = 2 * s.decoder_layers * d
         if out is None:
             out = torch.empty((2 * s.decoder_layers, B, self.H, T, _HD), device=self.device, dtype=self.dtype)
@@ -343,7 +380,7 @@ class WhisperEngine:
         import copy
 
         other = copy.copy(self)
-        other._enc, other._enc_split, other._enc_streams = {}, {}, []
+        other._enc, other._enc_split, other._enc_streams, other._kv_stage = {}, {}, [], {}
         return other
 
     def new_session(self, B: int, enc: torch.Tensor | None = None, beams: int = 1) -> "DecodeSession":

@@ -147,12 +147,16 @@ class KWhisperForConditionalGeneration:
         return self
 
     @classmethod
-    def from_state_dict(cls, shape, state_dict, *, dtype=torch.bfloat16, device="cuda", generation_config=None):
+    def from_state_dict(cls, shape, state_dict, *, dtype=torch.bfloat16, device="cuda", generation_config=None,
+                        cross_kv_dtype=None):
+        """``cross_kv_dtype``: None / "bf16" (the default engine) or "fp8_e4m3" (WhisperEngine: the cross-attention K/V
+        cache as e4m3 codes with per-channel scales; bf16 engine, greedy decoding only)."""
         shape = PRESETS[shape] if isinstance(shape, str) else shape
-        return cls(WhisperEngine(shape, state_dict, dtype=dtype, device=device, generation_config=generation_config))
+        return cls(WhisperEngine(shape, state_dict, dtype=dtype, device=device, generation_config=generation_config,
+                                 cross_kv_dtype=cross_kv_dtype))
 
     @classmethod
-    def from_pretrained(cls, path_or_name, *, torch_dtype=torch.bfloat16, device="cuda", **kw):
+    def from_pretrained(cls, path_or_name, *, torch_dtype=torch.bfloat16, device="cuda", cross_kv_dtype=None, **kw):
         """Load a local HF checkpoint directory (config.json + *.safetensors).  No network access."""
         import json
 
@@ -182,7 +186,8 @@ class KWhisperForConditionalGeneration:
             for k, v in gj.items():
                 if hasattr(gen, k):
                     setattr(gen, k, v)
-        return cls.from_state_dict(shape, sd, dtype=torch_dtype, device=device, generation_config=gen)
+        return cls.from_state_dict(shape, sd, dtype=torch_dtype, device=device, generation_config=gen,
+                                   cross_kv_dtype=cross_kv_dtype)
 
     # ---- generate ---------------------------------------------------------------------------------
     def _session(self, B, beams=1):
@@ -240,6 +245,13 @@ class KWhisperForConditionalGeneration:
                                           "`return_token_timestamps` is not supported by the MI355X engine yet")
         if num_beams > 8:
             raise NotImplementedError("num_beams > 8 is not supported by the device beam search")
+        if getattr(self.engine, "cross_kv_fp8", False):
+            if num_beams > 1:
+                raise NotImplementedError("`num_beams` > 1 is not supported with cross_kv_dtype='fp8_e4m3' (the fp8 "
+                                          "cross-attention has no beam kernel); use num_beams=1 or the bf16 cache")
+            if kwargs.get("return_token_timestamps"):
+                raise NotImplementedError("`return_token_timestamps` is not supported with cross_kv_dtype='fp8_e4m3' "
+                                          "(the alignment weights read the bf16 K cache); use the bf16 cache")
         length_penalty = kwargs.get("length_penalty", getattr(gen, "length_penalty", 1.0))
         early_stopping = kwargs.get("early_stopping", getattr(gen, "early_stopping", False))
         max_new_tokens = kwargs.get("max_new_tokens")

@@ -462,6 +462,85 @@ class XqCrossPlan:
             L.check(_lib().kw_dec_xq_cross(self._ref, _s()), "kw_dec_xq_cross")
 
 
+def xq_cross_fp8_supported(M, d, H, S) -> bool:
+    """Whether kw_dec_xq_cross_fp8 covers the shape (M <= 32, d = 64 H <= 1280, S in six chunks of 225..256 keys)."""
+    return bool(_lib().kw_dec_xq_cross_fp8_supported(int(M), int(d), int(H), int(S)))
+
+
+class XqCrossFp8Plan:
+    """A pre-built ``kw_dec_xq_cross_fp8`` call: ``XqCrossPlan`` over the fp8 (e4m3) cross cache -- ``k`` / ``v`` one
+    layer's uint8 codes [M][H][S][64], ``k_scale`` / ``v_scale`` its f32 scales [M][H][64]; bitwise kw_dec_linear(xq)
+    then kw_cross_attn_step_fp8.  ``workspace``: kw_dec_xq_cross's (xq_cross_workspace_bytes), zero-filled."""
+
+    def __init__(self, x, W, M, d, H, *, ln, bias, scale, k, v, k_scale, v_scale, S, out, workspace, ldx=None,
+                 tag="xq_cross_fp8"):
+        _cuda(x, W, bias, k, v, k_scale, v_scale, out, workspace)
+        eps, colsum = ln
+        _cuda(colsum)
+        if (any(t.dtype != torch.bfloat16 for t in (x, W, out)) or any(t.dtype != torch.uint8 for t in (k, v))
+                or any(t.dtype != torch.float32 for t in (k_scale, v_scale))):
+            raise ValueError("kw_dec_xq_cross_fp8 takes bf16 activations, packed bf16 weights, uint8 (e4m3) K / V, f32 "
+                             "scales and a bf16 output")
+        if not all(t.is_contiguous() for t in (k, v, k_scale, v_scale)):
+            raise ValueError("kw_dec_xq_cross_fp8: K / V codes and scales must be contiguous")
+        ldx = d if ldx is None else ldx
+        if workspace.numel() * workspace.element_size() < xq_cross_workspace_bytes(M, d, H, S):
+            raise ValueError("kw_dec_xq_cross_fp8 workspace too small")
+        self.tag = tag
+        a = L.XqCrossFp8Args()
+        a.x, a.ldx, a.ln_eps, a.ln_colsum = x.data_ptr(), ldx, float(eps), colsum.data_ptr()
+        a.W, a.bias, a.scale = W.data_ptr(), bias.data_ptr() if bias is not None else None, float(scale)
+        a.M, a.d, a.H = M, d, H
+        a.k, a.v, a.S = k.data_ptr(), v.data_ptr(), S
+        a.k_scale, a.v_scale = k_scale.data_ptr(), v_scale.data_ptr()
+        a.out, a.workspace = out.data_ptr(), workspace.data_ptr()
+        a.ws_bytes = workspace.numel() * workspace.element_size()
+        self._a = a
+        self._ref = ctypes.byref(a)
+        self._keep = (x, W, bias, colsum, k, v, k_scale, v_scale, out, workspace)
+        self._targs = (x, W, bias, colsum, k, v, k_scale, v_scale, out, workspace, [ldx, M, d, H, S], float(eps),
+                       float(scale))
+
+    def __call__(self):
+        if _BACKEND == "torch":
+            _kw().dec_xq_cross_fp8(*self._targs)
+        else:
+            L.check(_lib().kw_dec_xq_cross_fp8(self._ref, _s()), "kw_dec_xq_cross_fp8")
+
+
+def cross_kv_quant(x, codes, scales):
+    """kw_cross_kv_quant: ``x`` bf16 [..., S, 64] (contiguous; the leading dims are the call's tiles) -> ``codes`` uint8 of
+    x's shape (OCP e4m3fn) and ``scales`` f32 [..., 64], the format of include/kwhisper.h "fp8 cross K/V"."""
+    _cuda(x, codes, scales)
+    if x.dtype != torch.bfloat16 or codes.dtype != torch.uint8 or scales.dtype != torch.float32:
+        raise ValueError("kw_cross_kv_quant takes bf16 K / V, uint8 codes and f32 scales")
+    if x.dim() < 2 or not (x.is_contiguous() and codes.is_contiguous() and scales.is_contiguous()):
+        raise ValueError("kw_cross_kv_quant takes contiguous [..., S, head_dim] tensors")
+    S, hd = x.shape[-2], x.shape[-1]
+    n = x.numel() // (S * hd)
+    if codes.numel() != x.numel() or scales.numel() != n * hd:
+        raise ValueError("kw_cross_kv_quant: codes must have x's size and scales one value per (tile, head dim)")
+    if _BACKEND == "torch":
+        _kw().cross_kv_quant(x, n, S, hd, codes, scales)
+        return
+    L.check(_lib().kw_cross_kv_quant(_p(x), n, S, hd, _p(codes), _p(scales), _s()), "kw_cross_kv_quant")
+
+
+def cross_attn_step_fp8(q, B, q_len, H, hd, k, v, k_scale, v_scale, S, out):
+    """kw_cross_attn_step_fp8: ``cross_attn_step`` over the fp8 cache (one layer's codes and scales); no workspace."""
+    _cuda(q, k, v, k_scale, v_scale, out)
+    if not all(t.is_contiguous() for t in (k, v, k_scale, v_scale)):
+        raise ValueError("kw_cross_attn_step_fp8: K / V codes and scales must be contiguous")
+    if _BACKEND == "torch":
+        _kw().cross_attn_step_fp8(q, B, q_len, H, hd, k, v, k_scale, v_scale, S, out)
+        return
+    if (q.dtype != torch.bfloat16 or out.dtype != torch.bfloat16 or k.dtype != torch.uint8 or v.dtype != torch.uint8
+            or k_scale.dtype != torch.float32 or v_scale.dtype != torch.float32):
+        raise ValueError("kw_cross_attn_step_fp8 takes a bf16 query and output, uint8 (e4m3) K / V and f32 scales")
+    L.check(_lib().kw_cross_attn_step_fp8(_p(q), B, q_len, H, hd, _p(k), _p(v), _p(k_scale), _p(v_scale), S, _p(out),
+                                          _s()), "kw_cross_attn_step_fp8")
+
+
 def cross_attn_workspace_bytes(B, q_len, H, hd, S) -> int:
     return _ws_bytes("cross_attn", B, q_len, H, hd, S)
 

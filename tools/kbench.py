@@ -5,6 +5,7 @@ Times each decode-step kernel at large-v3 shapes (B=32) cycling over 32 distinct
 buffers (as the 32 decoder layers do) so the 256 MB Infinity Cache cannot serve repeats.
 
     python tools/kbench.py [--reps 20]
+    python tools/kbench.py --only xq_cross_fp8 [--tiled] [--rounds 3]   # the fp8 cross block against the bf16 one
 """
 from __future__ import annotations
 
@@ -55,8 +56,50 @@ def timeit(fns, reps):
     return e0.elapsed_time(e1) * 1e3 / (reps * len(fns))  # us per launch
 
 
+def xq_cross_fp8_ab(a, dev, hb, out, B, d, H, S, nl):
+    """The fused cross block over the fp8 (e4m3) cache against the fused bf16 block: the same query projection, nl
+    distinct layers' K / V each (the fp8 codes are those bf16 layers quantised by kw_cross_kv_quant), timed in
+    alternating rounds in this one process.  Bytes are the algorithm's: K / V (+ scales) + the projection's weights."""
+    cross = [torch.randn(2, B, H, S, 64, device=dev).bfloat16() for _ in range(nl)]
+    codes = [torch.empty(2, B, H, S, 64, device=dev, dtype=torch.uint8) for _ in range(nl)]
+    scales = [torch.empty(2, B, H, 64, device=dev) for _ in range(nl)]
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for c, cd, sc in zip(cross, codes, scales):
+        ops.cross_kv_quant(c, cd, sc)
+    e1.record()
+    e1.synchronize()
+    quant_ms = e0.elapsed_time(e1)
+    Wq = [ops.pack_weight((torch.randn(d, d, device=dev) / d ** 0.5).bfloat16()) for _ in range(nl)]
+    cs, bq = torch.zeros(d, device=dev), torch.zeros(d, device=dev)
+    hbd = hb[:, :d].contiguous()
+    ldx = None
+    if a.tiled:
+        hbd, ldx = ops.act_tile(hbd), ops.KW_LD_TILED
+    w16 = torch.zeros(ops.xq_cross_workspace_bytes(B, d, H, S) // 4 + 1, device=dev)
+    w8 = torch.zeros(ops.xq_cross_workspace_bytes(B, d, H, S) // 4 + 1, device=dev)
+    p16 = [ops.XqCrossPlan(hbd, Wq[i], B, d, H, ln=(1e-5, cs), bias=bq, scale=0.125, k=cross[i][0], v=cross[i][1], S=S,
+                           out=out, workspace=w16, ldx=ldx) for i in range(nl)]
+    p8 = [ops.XqCrossFp8Plan(hbd, Wq[i], B, d, H, ln=(1e-5, cs), bias=bq, scale=0.125, k=codes[i][0], v=codes[i][1],
+                             k_scale=scales[i][0], v_scale=scales[i][1], S=S, out=out, workspace=w8, ldx=ldx)
+          for i in range(nl)]
+    kv = 2 * B * H * S * 64
+    bytes16, bytes8 = kv * 2 + d * d * 2, kv + 2 * B * H * 64 * 4 + d * d * 2
+    reps = max(1, a.reps // 4)
+    rounds = {"bf16": [], "fp8": []}
+    for _ in range(a.rounds):
+        rounds["bf16"].append(round(timeit(p16, reps), 2))
+        rounds["fp8"].append(round(timeit(p8, reps), 2))
+    med = {k: sorted(v)[len(v) // 2] for k, v in rounds.items()}
+    return {"rounds_us": rounds, "median_us": med,
+            "bytes_per_us": {"bf16": round(bytes16 / med["bf16"]), "fp8": round(bytes8 / med["fp8"])},
+            "algorithmic_MB": {"bf16": round(bytes16 / 1e6, 1), "fp8": round(bytes8 / 1e6, 1)},
+            "quant_ms_per_layer": round(quant_ms / nl, 3), "layers": nl, "tiled": bool(a.tiled)}
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--rounds", type=int, default=3, help="alternating rounds of the xq_cross_fp8 A/B")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--layers", type=int, default=32)
     ap.add_argument("--only", default="", help="comma list of kernel names to run (default: all)")
@@ -111,7 +154,7 @@ def main():
         us = timeit(plans, a.reps)
         res[name] = {"us": round(us, 2), "GBps": round(N * K * 2 / us / 1e3, 1)}
     # attention kernels (and the fused decode blocks: kw_dec_xq_cross, kw_dec_qkv_self)
-    if not any(want(n) for n in ("cross_attn", "xq_cross", "self_attn", "qkv_self")):
+    if not any(want(n) for n in ("cross_attn", "xq_cross", "xq_cross_fp8", "self_attn", "qkv_self")):
         print(json.dumps(res))
         return
     q = torch.randn(B, d, device=dev).bfloat16()
@@ -137,6 +180,8 @@ def main():
         us = timeit(plans, max(1, a.reps // 4))
         res["xq_cross"] = {"us": round(us, 2), "GBps": round((2 * B * H * S * 64 * 2 + d * d * 2) / us / 1e3, 1)}
         del cross, Wq, plans
+    if "xq_cross_fp8" in only:  # (explicit only: it holds both caches, 7.9 + 3.9 GB at 32 layers)
+        res["xq_cross_fp8"] = xq_cross_fp8_ab(a, dev, hb, out, B, d, H, S, nl)
     if not want("self_attn") and not want("qkv_self"):
         print(json.dumps(res))
         return
