@@ -462,7 +462,8 @@ size_t kw_sample_step_workspace(int64_t B);
 
 /* log_softmax of each row's raw f32 logits (utils.py:3380), the Whisper processors on the log-probs
  * (as kw_greedy_step, with the row's own history ids[r][0..L) ), and the row's k best processed
- * log-probs, descending, ties to the lower token id: cand_val/cand_idx [R][k], k <= 16. */
+ * log-probs, descending, ties to the lower token id: cand_val/cand_idx [R][k], k <= 16.  A row with
+ * fewer than k finite scores goes on with -inf and its lowest -inf token ids, as a top-k over the row. */
 typedef struct {
   const float* logits;
   int64_t R, V;
@@ -496,7 +497,16 @@ size_t kw_beam_logprobs_workspace(int64_t R);
  * reference loop continues) / *done, and *cur_len += 1.  Initial state: ids rows = prompt, bp rows =
  * own row for p < P (or bp NULL when the K/V cache is not shared), run_scores = [0, -1e9, ...] per
  * item, fin_seq = fill_id, fin_score = -1e9, fin_len = fin_flag = 0, unsat = 1, counter = go = done = 0.
- * 2 <= num_beams <= 8, max_length <= 512, fin_stride / ids_stride / bp_stride >= max_length. */
+ * 2 <= num_beams <= 8, max_length <= 512, fin_stride / ids_stride / bp_stride >= max_length.
+ * A step writes positions [0, cur_len] of the ids / bp rows and [0, max_length) of the fin_seq rows;
+ * what a row holds beyond is left alone.
+ * The continuations come from each row's 2*num_beams candidates, not from the whole vocabulary.  That
+ * is the reference's flat top-k over beams x vocab except when a row's score absorbs log-prob
+ * differences: a token outside the row's candidates whose f32 sum (log-prob + score) equals that of
+ * a candidate, has the lower id and is among the item's 2*num_beams best sums.  The reference then
+ * keeps the lower ids of the tie, this step the higher log-probs.  A row with a -1e9 score (ulp 64)
+ * ties all its tokens above -32 this way; such a row is reached only when the other rows of its item
+ * hold fewer than 2*num_beams finite candidates between them. */
 typedef struct {
   int64_t B;
   int32_t num_beams;

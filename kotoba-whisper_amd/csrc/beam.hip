@@ -5,7 +5,8 @@
 //    log_softmax of the raw f32 logits (:3380), the Whisper processors on the log-probs (Suppress ->
 //    SuppressAtBegin -> WhisperTimeStamp, processors.h; :3381), and the row's K best processed
 //    log-probs (K = 2 * num_beams: the global top-K over beams x vocab of log-prob + beam score is
-//    always inside the union of the rows' top-K, adding a per-row constant keeps a row's order).
+//    inside the union of the rows' top-K, adding a per-row constant keeps a row's order -- up to the f32
+//    ties a score makes of different log-probs, the one exception include/kwhisper.h states).
 //  kw_beam_select (one workgroup per batch item):
 //    _get_top_k_continuations (:3077), the MaxLength / EOS stopping criteria on the K continuations,
 //    _get_running_beams_for_next_iteration (:3131), _update_finished_beams (:3153, length penalty,
@@ -114,7 +115,6 @@ __global__ __launch_bounds__(ST) void beam_logprobs_kernel(kw_beam_logprobs_args
   __shared__ float shf[ST / 64];
   __shared__ int shi[ST / 64][2];
   __shared__ RowState st_sh;
-  __shared__ int win_t;
   if (*a.done) return;
   const int r = blockIdx.x;
   const int tid = threadIdx.x;
@@ -141,75 +141,52 @@ __global__ __launch_bounds__(ST) void beam_logprobs_kernel(kw_beam_logprobs_args
                           a.max_initial_ts, &fin, shi, &st_sh);
   if (st.rt) timestamp_rule(st, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, V, lp, shf);
 
-  // per-thread sorted top-K of its strided slice, then K rounds of a block arg-max over the heads
-  float tv[KMAX];
-  int ti[KMAX];
+  // per-thread sorted top-K of its strided slice as 64-bit (score, token) keys ordered like better() -- a -inf
+  // score is a key too, so a row with fewer than K finite scores goes on with its lowest -inf tokens, as the
+  // reference's top-k does -- then K rounds of a block maximum over the heads
+  uint64_t tk[KMAX];
 #pragma unroll
-  for (int i = 0; i < KMAX; ++i) {
-    tv[i] = -INFINITY;
-    ti[i] = 0x7fffffff;
-  }
+  for (int i = 0; i < KMAX; ++i) tk[i] = 0;
   for (int v = tid; v < V; v += ST) {
-    const float sv = process(st, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, v, lp(v));
-    if (!better(sv, v, tv[KMAX - 1], ti[KMAX - 1])) continue;  // (keeps KMAX >= K per thread)
-    // insert (v increases along the slice, so an equal value goes after the existing ones)
-    float cv = sv;
-    int ci = v;
+    uint64_t c = bkey(process(st, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, v, lp(v)), v);
+    if (c <= tk[KMAX - 1]) continue;  // (keeps KMAX >= K per thread)
 #pragma unroll
     for (int i = 0; i < KMAX; ++i) {
-      if (better(cv, ci, tv[i], ti[i])) {
-        const float t1 = tv[i];
-        const int t2 = ti[i];
-        tv[i] = cv;
-        ti[i] = ci;
-        cv = t1;
-        ci = t2;
+      if (c > tk[i]) {
+        const uint64_t t1 = tk[i];
+        tk[i] = c;
+        c = t1;
       }
     }
   }
+  __shared__ uint64_t wk[ST / 64];
+  __shared__ uint64_t win_k;
   int head = 0;
   for (int k = 0; k < K; ++k) {
-    float hv = -INFINITY;
-    int hi = 0x7fffffff;
+    uint64_t hk = 0;
 #pragma unroll
     for (int i = 0; i < KMAX; ++i)
-      if (i == head) {
-        hv = tv[i];
-        hi = ti[i];
-      }
-    float bv = hv;
-    int bi = hi, bt = tid;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const float ov = __shfl_xor(bv, o, 64);
-      const int oi = __shfl_xor(bi, o, 64), ot = __shfl_xor(bt, o, 64);
-      if (better(ov, oi, bv, bi)) {
-        bv = ov;
-        bi = oi;
-        bt = ot;
-      }
-    }
-    if ((tid & 63) == 0) {
-      shf[tid >> 6] = bv;
-      shi[tid >> 6][0] = bi;
-      shi[tid >> 6][1] = bt;
-    }
+      if (i == head) hk = tk[i];
+    const uint64_t wg = wave_max_u64(hk);
+    if ((tid & 63) == 0) wk[tid >> 6] = wg;
     __syncthreads();
     if (tid == 0) {
-      float gv = shf[0];
-      int gi = shi[0][0], gt = shi[0][1];
-      for (int w = 1; w < ST / 64; ++w)
-        if (better(shf[w], shi[w][0], gv, gi)) {
-          gv = shf[w];
-          gi = shi[w][0];
-          gt = shi[w][1];
-        }
-      a.cand_val[(int64_t)r * K + k] = gv;
-      a.cand_idx[(int64_t)r * K + k] = gi == 0x7fffffff ? 0 : gi;
-      win_t = gt;
+      uint64_t g = wk[0];
+      for (int w = 1; w < ST / 64; ++w) g = wk[w] > g ? wk[w] : g;
+      win_k = g;
+      if (g == 0) {  // fewer than K tokens in the row
+        a.cand_val[(int64_t)r * K + k] = -INFINITY;
+        a.cand_idx[(int64_t)r * K + k] = 0;
+      }
     }
     __syncthreads();
-    if (tid == win_t) ++head;
+    const uint64_t g = win_k;
+    if (g != 0 && hk == g) {  // token ids are unique: one thread holds the winner; it writes its own f32 value
+      const int v = bkey_idx(g);
+      a.cand_val[(int64_t)r * K + k] = process(st, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, v, lp(v));
+      a.cand_idx[(int64_t)r * K + k] = v;
+      ++head;
+    }
     __syncthreads();
   }
 }
@@ -530,10 +507,21 @@ __global__ __launch_bounds__(BT_S) void beam_logprobs_split_kernel(kw_beam_logpr
   uint64_t kk[3];
 #pragma unroll
   for (int t = 0; t < 3; ++t) kk[t] = ci3[t] != 0x7fffffff ? bkey(c[t], ci3[t]) : 0;
+  int nf = -1;  // the row's finite candidates, once the places have run past them
   for (int j = 0; j < K; ++j) {
     uint64_t b = kk[0] > kk[1] ? kk[0] : kk[1];
     b = b > kk[2] ? b : kk[2];
     const uint64_t g = wave_best_key(b);
+    if (nf < 0 && (g == 0 || !(bkey_val(g) > -INFINITY))) nf = j;
+    // a -inf place names the lowest token that is -inf (the reference's top-k).  Under the text ban those are
+    // the text tokens, which the timestamp list does not hold: ts_begin places of them, then the list's own
+    if (ban && nf >= 0 && j - nf < st.ts_begin) {
+      if (lane == 0) {
+        a.cand_val[(int64_t)r * K + j] = -INFINITY;
+        a.cand_idx[(int64_t)r * K + j] = j - nf;
+      }
+      continue;
+    }
     if (g == 0) {  // no candidate left (cannot happen with a sane config): as the reference's -inf / 0
       if (lane == 0) {
         a.cand_val[(int64_t)r * K + j] = -INFINITY;
@@ -694,16 +682,17 @@ __global__ __launch_bounds__(BT) void beam_select_kernel(kw_beam_select_args a) 
   block_topk(m_val, m_key, nb + K, nb, fin_pos, shf, shi);
   // 5. the new finished set: old entries come from the LDS copy, new ones are a candidate's parent
   //    history + its token, fill (pad) beyond -- as the reference's static-shape sequences
-  const int Tf = (int)a.fin_stride;
-  for (int i = tid; i < nb * Tf; i += BT) {
-    const int j = i / Tf, p = i - j * Tf;
+  //    (positions < max_length only: what a row holds beyond, up to fin_stride, is the caller's)
+  const int Tf = (int)a.fin_stride, Tm = a.max_length;
+  for (int i = tid; i < nb * Tm; i += BT) {
+    const int j = i / Tm, p = i - j * Tm;
     fst[j][p] = (int)a.fin_seq[((int64_t)b * nb + j) * Tf + p];
   }
   __shared__ int fin_src[NBMAX];
   if (tid < nb) fin_src[tid] = fin_pos[tid];
   __syncthreads();
-  for (int i = tid; i < nb * Tf; i += BT) {
-    const int s = i / Tf, p = i - s * Tf;
+  for (int i = tid; i < nb * Tm; i += BT) {
+    const int s = i / Tm, p = i - s * Tm;
     const int src = fin_src[s];
     int v;
     if (src < nb) {
@@ -808,7 +797,7 @@ extern "C" int kw_beam_logprobs(const kw_beam_logprobs_args* a, kw_stream_t stre
 extern "C" int kw_beam_select(const kw_beam_select_args* a, kw_stream_t stream) {
   if (!a || a->B <= 0 || a->num_beams < 2 || a->num_beams > NBMAX || a->V <= 0 || !a->cand_val || !a->cand_idx ||
       !a->ids || !a->run_scores || !a->fin_seq || !a->fin_score || !a->fin_len || !a->fin_flag ||
-      !a->unsat || !a->cur_len || !a->counter || !a->go || !a->done || !a->item_flags || a->fin_stride > TMAX ||
+      !a->unsat || !a->cur_len || !a->counter || !a->go || !a->done || !a->item_flags ||
       a->ids_stride < a->max_length || a->fin_stride < a->max_length || a->max_length > TMAX ||
       (a->bp && a->bp_stride < a->max_length))
     return kw_set_error_msg(KW_EINVAL, "kw_beam_select: invalid arguments (2 <= num_beams <= 8, max_length <= 512)");

@@ -156,82 +156,112 @@ def _take(a: np.ndarray, idx: np.ndarray) -> np.ndarray:
     return np.take_along_axis(a, idx, axis=1)
 
 
+def beam_init(prompt: np.ndarray, num_beams: int, max_length: int, fill: int) -> dict:
+    """The state ``_beam_search`` starts from (utils.py:3300-3345) for a (B, P) prompt."""
+    f32 = np.float32
+    B, P = prompt.shape
+    nb = num_beams
+    running = np.full((B, nb, max_length), fill, dtype=np.int64)
+    running[:, :, :P] = prompt[:, None, :]
+    run_scores = np.zeros((B, nb), f32)
+    run_scores[:, 1:] = f32(-1.0e9)
+    run_bi = np.full((B, nb, max_length - P), -1, np.int32)
+    return dict(running=running, run_scores=run_scores, sequences=running.copy(),
+                beam_scores=np.full((B, nb), f32(-1.0e9), f32), fin=np.zeros((B, nb), bool),
+                fin_len=np.zeros((B, nb), np.int32), unsat=np.ones((B, 1), bool), run_bi=run_bi,
+                beam_idx=run_bi.copy(), cur_len=P)
+
+
+def beam_step(lp: np.ndarray, state: dict, *, eos: int, max_length: int, begin_index: int,
+              length_penalty: float = 1.0, early_stopping=False):
+    """One iteration of ``_beam_search``'s loop after the processors (utils.py:3383-3470): ``lp`` is the
+    processed log-probs (B, nb, V) f32 of the running beams, ``state`` a dict as ``beam_init`` makes it
+    (not modified).  Returns (next state, info); info holds ``go`` (the loop condition), ``hits`` (B, 2 nb:
+    the stopping criteria on the kept continuations), their ``parent`` beam, ``tok`` and summed score
+    ``topk_lp``, and the picks ``run_pick`` / ``fin_pick`` of the running and finished sets.  The finished
+    length of every finished entry is ``fin_len`` of the next state."""
+    f32 = np.float32
+    NEG = f32(-1.0e9)
+    P = begin_index
+    running, run_scores, run_bi = state["running"], state["run_scores"], state["run_bi"]
+    sequences, beam_scores, beam_idx = state["sequences"], state["beam_scores"], state["beam_idx"]
+    fin, fin_len, unsat, cur_len = state["fin"], state["fin_len"], state["unsat"], state["cur_len"]
+    B, nb, V = lp.shape
+    keep = 2 * nb  # max(2, 1 + n_eos) * num_beams with one EOS id (:3289)
+    top_mask = np.arange(keep) < nb
+    lp = (lp + run_scores[:, :, None]).astype(f32).reshape(B, nb * V)
+    # c. top-K continuations (:3077-3129)
+    idx = _topk(lp, keep)
+    topk_lp = np.take_along_axis(lp, idx, axis=1)
+    cur_beam = idx // V
+    tok = idx % V
+    topk_bi = _take(run_bi, cur_beam).copy()
+    topk_seq = _take(running, cur_beam).copy()
+    topk_seq[:, :, cur_len] = tok
+    topk_bi[:, :, cur_len - P] = cur_beam + np.arange(B)[:, None] * nb
+    # d. stopping criteria: MaxLength on the new length, EOS on the new token
+    hits = np.full((B, keep), cur_len + 1 >= max_length) | (tok == eos)
+    # e. running beams (:3131-3151)
+    trl = (topk_lp + hits.astype(f32) * NEG).astype(f32)
+    nidx = _topk(trl, nb)
+    running = _take(topk_seq, nidx)
+    run_scores = np.take_along_axis(trl, nidx, axis=1)
+    run_bi = _take(topk_bi, nidx)
+    # f. finished beams (:3153-3205)
+    did = hits & top_mask[None, :]
+    tl = (topk_lp / f32((cur_len + 1 - P) ** length_penalty)).astype(f32)
+    full = np.all(fin, axis=-1, keepdims=True) & (early_stopping is True)
+    tl = tl + full.astype(f32) * NEG
+    tl = tl + (~unsat).astype(f32) * NEG
+    tl = (tl + (~did).astype(f32) * NEG).astype(f32)
+    m_seq = np.concatenate([sequences, topk_seq], 1)
+    m_scores = np.concatenate([beam_scores, tl], 1)
+    m_bi = np.concatenate([beam_idx, topk_bi], 1)
+    m_fin = np.concatenate([fin, did], 1)
+    m_len = np.concatenate([fin_len, np.full((B, keep), cur_len + 1 - P, np.int32)], 1)
+    midx = _topk(m_scores, nb)
+    sequences, beam_scores = _take(m_seq, midx), np.take_along_axis(m_scores, midx, axis=1)
+    beam_idx, fin = _take(m_bi, midx), np.take_along_axis(m_fin, midx, axis=1)
+    fin_len = np.take_along_axis(m_len, midx, axis=1)
+    # g. early-stop heuristic (:3008-3053), loop condition (:3055-3075)
+    cur_len += 1
+    bhl = (max_length - P) if (early_stopping == "never" and length_penalty > 0.0) else (cur_len - P)
+    best_run = (run_scores[:, :1] / f32(bhl ** length_penalty)).astype(f32)
+    worst_fin = np.where(fin, beam_scores.min(1, keepdims=True), NEG)
+    unsat = unsat & np.any(best_run > worst_fin, axis=-1, keepdims=True)
+    go = bool(unsat.any() and not (fin.all() and early_stopping is True) and not hits.all())
+    nxt = dict(running=running, run_scores=run_scores, sequences=sequences, beam_scores=beam_scores, fin=fin,
+               fin_len=fin_len, unsat=unsat, run_bi=run_bi, beam_idx=beam_idx, cur_len=cur_len)
+    info = dict(go=go, hits=hits, parent=cur_beam, tok=tok, topk_lp=topk_lp, run_pick=nidx, fin_pick=midx)
+    return nxt, info
+
+
 def beam_search(model: WhisperNP, enc: np.ndarray, prompt: np.ndarray, gen: dict, max_length: int,
                 begin_index: int, return_timestamps: bool, num_beams: int, length_penalty: float = 1.0,
                 early_stopping=False) -> np.ndarray:
     """``GenerationMixin._beam_search`` (utils.py:3208-3527), num_return_sequences = 1.
     Returns (B, prompt + generated) ids of the best beam per item, filled with pad_token_id."""
-    f32 = np.float32
-    NEG = f32(-1.0e9)
     pad, eos = gen["pad_token_id"], gen["eos_token_id"]
     B, P = prompt.shape
     nb = num_beams
-    keep = 2 * nb  # max(2, 1 + n_eos) * num_beams with one EOS id (:3289)
-    fill = pad if pad is not None else eos
-    running = np.full((B, nb, max_length), fill, dtype=np.int64)
-    running[:, :, :P] = prompt[:, None, :]
-    sequences = running.copy()
-    run_scores = np.zeros((B, nb), f32)
-    run_scores[:, 1:] = NEG
-    beam_scores = np.full((B, nb), NEG, f32)
-    fin = np.zeros((B, nb), bool)
-    unsat = np.ones((B, 1), bool)
-    run_bi = np.full((B, nb, max_length - P), -1, np.int32)
-    beam_idx = run_bi.copy()
-    top_mask = np.arange(keep) < nb
+    st = beam_init(prompt, nb, max_length, pad if pad is not None else eos)
     cache = model.new_cache(np.repeat(enc, nb, axis=0))
     logits = model.decode(np.repeat(prompt, nb, axis=0), cache)[:, -1]
     V = logits.shape[-1]
-    cur_len = P
     while True:
-        flat_hist = running.reshape(B * nb, max_length)[:, :cur_len]
+        cur_len = st["cur_len"]
+        flat_hist = st["running"].reshape(B * nb, max_length)[:, :cur_len]
         lp = process_logits(flat_hist, _log_softmax(logits), gen, begin_index, return_timestamps)
-        lp = (lp.reshape(B, nb, V) + run_scores[:, :, None]).astype(f32).reshape(B, nb * V)
-        # c. top-K continuations (:3077-3129)
-        idx = _topk(lp, keep)
-        topk_lp = np.take_along_axis(lp, idx, axis=1)
-        cur_beam = idx // V
-        tok = idx % V
-        topk_bi = _take(run_bi, cur_beam).copy()
-        topk_seq = _take(running, cur_beam).copy()
-        topk_seq[:, :, cur_len] = tok
-        topk_bi[:, :, cur_len - P] = cur_beam + np.arange(B)[:, None] * nb
-        # d. stopping criteria: MaxLength on the new length, EOS on the new token
-        hits = np.full((B, keep), cur_len + 1 >= max_length) | (tok == eos)
-        # e. running beams (:3131-3151)
-        trl = (topk_lp + hits.astype(f32) * NEG).astype(f32)
-        nidx = _topk(trl, nb)
-        running = _take(topk_seq, nidx)
-        run_scores = np.take_along_axis(trl, nidx, axis=1)
-        run_bi = _take(topk_bi, nidx)
-        # f. finished beams (:3153-3205)
-        did = hits & top_mask[None, :]
-        tl = (topk_lp / f32((cur_len + 1 - P) ** length_penalty)).astype(f32)
-        full = np.all(fin, axis=-1, keepdims=True) & (early_stopping is True)
-        tl = tl + full.astype(f32) * NEG
-        tl = tl + (~unsat).astype(f32) * NEG
-        tl = (tl + (~did).astype(f32) * NEG).astype(f32)
-        m_seq = np.concatenate([sequences, topk_seq], 1)
-        m_scores = np.concatenate([beam_scores, tl], 1)
-        m_bi = np.concatenate([beam_idx, topk_bi], 1)
-        m_fin = np.concatenate([fin, did], 1)
-        midx = _topk(m_scores, nb)
-        sequences, beam_scores = _take(m_seq, midx), np.take_along_axis(m_scores, midx, axis=1)
-        beam_idx, fin = _take(m_bi, midx), np.take_along_axis(m_fin, midx, axis=1)
-        # g. cache reorder, early-stop heuristic (:3008-3053), loop condition (:3055-3075)
-        model.reorder(cache, run_bi[..., cur_len - P].reshape(-1))
-        cur_len += 1
-        bhl = (max_length - P) if (early_stopping == "never" and length_penalty > 0.0) else (cur_len - P)
-        best_run = (run_scores[:, :1] / f32(bhl ** length_penalty)).astype(f32)
-        worst_fin = np.where(fin, beam_scores.min(1, keepdims=True), NEG)
-        unsat = unsat & np.any(best_run > worst_fin, axis=-1, keepdims=True)
-        go = unsat.any() and not (fin.all() and early_stopping is True) and not hits.all()
-        if not go:
+        st, info = beam_step(lp.reshape(B, nb, V), st, eos=eos, max_length=max_length, begin_index=P,
+                             length_penalty=length_penalty, early_stopping=early_stopping)
+        # cache reorder (:3445-3456)
+        model.reorder(cache, st["run_bi"][..., cur_len - P].reshape(-1))
+        if not info["go"]:
             break
-        logits = model.decode(running.reshape(B * nb, max_length)[:, cur_len - 1: cur_len], cache)[:, -1]
-    best_bi = beam_idx[:, 0]
+        logits = model.decode(st["running"].reshape(B * nb, max_length)[:, cur_len: cur_len + 1], cache)[:, -1]
+    best_bi = st["beam_idx"][:, 0]
     max_gen = int(((best_bi + 1) != 0).sum(1).max())
-    return sequences[:, 0, : P + max_gen]
+    return st["sequences"][:, 0, : P + max_gen]
 
 
 def _retrieve_segment(seq, ts_begin, seek_num_frames, time_offset, input_stride=2, time_precision=0.02,
