@@ -183,6 +183,22 @@ int kw_self_attn_step(int dtype, const void* qkv, int64_t B, int64_t q_len, int6
                       kw_stream_t stream);
 size_t kw_self_attn_workspace(int64_t B, int64_t H, int64_t t_max);
 
+/* kw_self_attn_step with a per-row first key, for left-padded prompts (TF generation_whisper.py:1908: the
+ * decoder_attention_mask of a conditioned long-form pass; the pads sit in front of a row and keep their positions).
+ * key_start: [B] int32 on the device.  Row b attends key positions k with key_start[b] <= k <= own position; keys
+ * below key_start[b] are never read (the cache may hold anything there).  The new positions' K/V are appended for
+ * every row as in kw_self_attn_step.  A query position below its row's key_start (a pad) has no key: its output
+ * row is zeros.  bp, workspace and the dtypes as in kw_self_attn_step.  key_start all zero: q_len == 1 writes
+ * kw_self_attn_step's bits in both dtypes.  q_len > 1, f32: one workgroup per (row, head, query position) with
+ * kw_self_attn_step's summation order per query, the same bits again.  q_len > 1, bf16: a causal MFMA tile kernel
+ * (one wave per 16 query positions, 32-key tiles), within bf16 rounding of kw_self_attn_step;
+ * dtype | KW_SELF_ATTN_PER_QUERY selects the per-query form for bf16 too (bitwise kw_self_attn_step; measurements). */
+#define KW_SELF_ATTN_PER_QUERY 0x100
+int kw_self_attn_step_masked(int dtype, const void* qkv, int64_t B, int64_t q_len, int64_t H, int64_t hd,
+                             void* k_cache, void* v_cache, int64_t t_max, const int32_t* cur_len,
+                             const int32_t* key_start, const int32_t* bp, int64_t bp_stride, void* out,
+                             void* workspace, size_t ws_bytes, kw_stream_t stream);
+
 /* The self-attention block of one greedy decode step in ONE launch (bf16): the LayerNorm-fused QKV projection
  * (TF modeling_whisper.py:446,469-471; q * head_dim^-0.5 :309) and the self-attention step over the static
  * cache with the new key / value appended (:469-480, cache_utils.py:127-145) -- kw_dec_linear(qkv) followed by

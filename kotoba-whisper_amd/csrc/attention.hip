@@ -14,7 +14,11 @@
 // Encoder f32 path: exact-fp32 reference-order kernel for the parity mode.
 // Decoder self-attention (K10): static KV cache append + attention; one new position per row splits
 //   the keys into <= 256-key chunks like the cross-attention (prefill, q_len > 1: one workgroup per
-//   (b, h) walking the queries).
+//   (b, h) walking the queries).  kw_self_attn_step_masked: the same with a per-row first key (left-padded
+//   prompts of a conditioned long-form pass), kernels of their own -- self_attn_step1_masked (chunks start at
+//   the row's first key), self_attn_prefill_masked (f32: one workgroup per (b, h, query position), a prompt of
+//   ~228 positions runs side by side) and self_attn_prefill_masked_mfma (bf16: one wave per 16 query positions,
+//   S^T = K Q^T and O^T = V^T P^T on v_mfma_f32_16x16x32_bf16 over 32-key tiles).
 // Decoder cross-attention (K11): split-S partial softmax over cached encoder K/V in <= 256-key chunks,
 //   8 lanes per key row so every K and V load is a coalesced 1-KB wave access, and every load of the
 //   chunk (64 KB) issued before the first score; the last-arriving chunk combines the partials in the
@@ -1769,6 +1773,243 @@ struct CrossGeo {
   bool row_groups_ok() const { return chunk > 32 * ROW_JV && last > 32 * ROW_JV; }
 };
 
+// ------------------------------------------------------------------------------------------------
+// kw_self_attn_step_masked's kernels.  They stand behind every other kernel of this file so that those keep
+// their place in the code object.
+// ------------------------------------------------------------------------------------------------
+// The same append and causal attention with a per-row first key (left-padded prompts: row b attends keys
+// [key_start[b], own position], the keys below are never read), one workgroup per (row, head, query position):
+// the query positions of a long prompt run side by side instead of one after the other.  A query is summed by
+// attend_rows in self_attn_step's order, so key_start == 0 gives that kernel's bits.  A query position below
+// its row's key_start (a pad) has no key: its output is zero.  Each workgroup appends its own position's K/V.
+template <typename T>
+__global__ __launch_bounds__(256) void self_attn_prefill_masked(const T* __restrict__ qkv, int q_len, int H,
+                                                                T* __restrict__ kc, T* __restrict__ vc, int t_max,
+                                                                const int32_t* __restrict__ cur_len,
+                                                                const int32_t* __restrict__ key_start,
+                                                                T* __restrict__ out) {
+  __shared__ float sc[512];
+  __shared__ float red[32][65];
+  __shared__ float stat[8];
+  const int bh = blockIdx.x, qi = blockIdx.y;
+  const int b = bh / H, h = bh - (bh / H) * H;
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int sub = lane & 7;
+  const int L = *cur_len;
+  const int d = H * HD;
+  const int p0 = L - q_len;
+  const int ks = max(key_start[b], 0);
+  T* kb = kc + ((int64_t)b * H + h) * t_max * HD;
+  T* vb = vc + ((int64_t)b * H + h) * t_max * HD;
+  const T* qrow = qkv + ((int64_t)b * q_len + qi) * 3 * d + h * HD;
+  if (tid < 8) {
+    copy8<T>(kb + (int64_t)(p0 + qi) * HD + tid * 8, qrow + d + tid * 8);
+    copy8<T>(vb + (int64_t)(p0 + qi) * HD + tid * 8, qrow + 2 * d + tid * 8);
+  }
+  T* orow = out + ((int64_t)b * q_len + qi) * d + h * HD;
+  if (ks > p0 + qi) {  // workgroup-uniform
+    if (tid < HD) TypeIO<T>::st(orow + tid, 0.f);
+    return;
+  }
+  auto kp = [&](int k) -> const T* {
+    return k < p0 ? kb + (int64_t)k * HD : qkv + ((int64_t)b * q_len + (k - p0)) * 3 * d + d + h * HD;
+  };
+  auto vp = [&](int k) -> const T* {
+    return k < p0 ? vb + (int64_t)k * HD : qkv + ((int64_t)b * q_len + (k - p0)) * 3 * d + 2 * d + h * HD;
+  };
+  float qv[8];
+  load8<T>(qrow + sub * 8, qv);
+  float m, l, o;
+  attend_rows<T>(qv, ks, p0 + qi + 1, kp, vp, sc, red, stat, m, l, o);
+  if (tid < HD) TypeIO<T>::st(orow + tid, o / l);
+}
+
+// self_attn_step1 with a per-row first key (a kernel of its own: self_attn_step1's code stays as it compiles
+// today).  Row b attends [ks, L), ks = key_start[b], in <= 256-key chunks that start at ks -- the keys below are
+// never read, and ks == 0 gives self_attn_step1's chunks and bits.  L - ks <= t_max <= 512: at most two chunks,
+// the workspace of kw_self_attn_workspace.  ks >= L (a pad position, no key): the output row is zero.
+template <typename T, bool BP>
+__global__ __launch_bounds__(256) void self_attn_step1_masked(const T* __restrict__ qkv, int H, T* __restrict__ kc,
+                                                              T* __restrict__ vc, int t_max,
+                                                              const int32_t* __restrict__ cur_len,
+                                                              const int32_t* __restrict__ key_start,
+                                                              const int32_t* __restrict__ bp, int bp_stride,
+                                                              float* __restrict__ ws, int* __restrict__ cnt,
+                                                              T* __restrict__ out) {
+  __shared__ float red[4][64];
+  __shared__ float stat[8];
+  __shared__ int last;
+  const int bh = blockIdx.x, split = blockIdx.y;
+  const int b = bh / H, h = bh - (bh / H) * H;
+  const int tid = threadIdx.x, sub = tid & 7;
+  const int L = *cur_len;
+  const int d = H * HD;
+  const int p0 = L - 1;
+  const int ks = max(key_start[b], 0);
+  const int k0 = ks + split * 256;
+  T* kb = kc + ((int64_t)b * H + h) * t_max * HD;
+  T* vb = vc + ((int64_t)b * H + h) * t_max * HD;
+  const T* row = qkv + (int64_t)b * 3 * d + h * HD;
+  T* orow = out + (int64_t)b * d + h * HD;
+  if (split == 0 && tid < 8) {
+    copy8<T>(kb + (int64_t)p0 * HD + tid * 8, row + d + tid * 8);
+    copy8<T>(vb + (int64_t)p0 * HD + tid * 8, row + 2 * d + tid * 8);
+  }
+  if (k0 >= L) {
+    if (split == 0 && tid < HD) TypeIO<T>::st(orow + tid, 0.f);
+    return;
+  }
+  const int ns = (L - ks + 255) / 256;
+  float qv[8];
+  load8<T>(row + sub * 8, qv);
+  float m, l, o;
+  const int k1 = min(L, k0 + 256);
+  const int kslot = (tid >> 6) * 8 + ((tid & 63) >> 3);
+  int32_t crow[8];
+  if constexpr (BP) {
+    const int32_t* bpr = bp + (int64_t)b * bp_stride;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) crow[j] = bpr[min(k0 + kslot + 32 * j, k1 - 1)];  // < L <= t_max <= bp_stride
+  } else {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) crow[j] = b;
+  }
+  auto slot = [&](int k, int j) -> int64_t { return ((int64_t)crow[j] * H + h) * t_max * HD + (int64_t)k * HD; };
+  attend_chunk<T>(qv, k0, k1,
+                  [&](int k, int j) -> const T* { return k < p0 ? kc + slot(k, j) : row + d; },
+                  [&](int k, int j) -> const T* { return k < p0 ? vc + slot(k, j) : row + 2 * d; }, red, stat, m, l, o);
+  if (ns == 1) {
+    if (tid < HD) TypeIO<T>::st(orow + tid, o / l);
+    return;
+  }
+  publish_and_combine<T>(ws + (int64_t)bh * 2 * (HD + 2), cnt + bh, ns, split, m, l, o, orow, &last);
+}
+
+// The bf16 prefill as a causal tile kernel: one wave per (row, head, 16 query positions), keys in tiles of 32 from the
+// row's first key.  Scores are computed transposed, S^T = K Q^T (v_mfma_f32_16x16x32_bf16: A = 16 keys x 32 dims, B =
+// 32 dims x 16 queries, both 16-B row loads), so a lane owns one query (column lane & 15) and the keys 4g + r of each
+// 16-key half (g = lane >> 4): the online softmax is in-lane plus two lane exchanges.  O^T = V^T P^T takes P^T straight
+// from those accumulators as the B operand -- its k slots (g, j) stand for keys 4g + j (j < 4) and 16 + 4g + j - 4 of
+// the tile, and V^T (A operand, through a row-major LDS image of the 32 V rows) is read in the same key order.  Keys
+// below key_start are never addressed (tiles start there); addresses past the tile's last key are clamped to it and
+// masked.  A pad query (no key) writes zeros.  The wave appends its own 16 positions' K/V.
+__global__ __launch_bounds__(64) void self_attn_prefill_masked_mfma(const bf16_t* __restrict__ qkv, int q_len, int H,
+                                                                    bf16_t* __restrict__ kc, bf16_t* __restrict__ vc,
+                                                                    int t_max, const int32_t* __restrict__ cur_len,
+                                                                    const int32_t* __restrict__ key_start,
+                                                                    bf16_t* __restrict__ out) {
+  constexpr int VLD = HD + 8;  // LDS row of 144 B: the 16-B row writes and the 2-B column reads spread over the banks
+  __shared__ __attribute__((aligned(16))) bf16_t vs[32 * VLD];
+  const int bh = blockIdx.x, q0 = blockIdx.y * 16;
+  const int b = bh / H, h = bh - (bh / H) * H;
+  const int lane = threadIdx.x, qn = lane & 15, g = lane >> 4;
+  const int L = *cur_len;
+  const int d = H * HD;
+  const int p0 = L - q_len;
+  const int ks = max(key_start[b], 0);
+  bf16_t* kb = kc + ((int64_t)b * H + h) * t_max * HD;
+  bf16_t* vb = vc + ((int64_t)b * H + h) * t_max * HD;
+  const bf16_t* rows = qkv + (int64_t)b * q_len * 3 * d + h * HD;  // row qi: rows + qi * 3d (+ d: k, + 2d: v)
+  for (int i = lane; i < 16 * 8; i += 64) {
+    const int qi = q0 + (i >> 3), c8 = (i & 7) * 8;
+    if (qi < q_len) {
+      copy8<bf16_t>(kb + (int64_t)(p0 + qi) * HD + c8, rows + (int64_t)qi * 3 * d + d + c8);
+      copy8<bf16_t>(vb + (int64_t)(p0 + qi) * HD + c8, rows + (int64_t)qi * 3 * d + 2 * d + c8);
+    }
+  }
+  const bool qok = q0 + qn < q_len;
+  const int qi = min(q0 + qn, q_len - 1);
+  const int pos = p0 + qi;
+  const int kend = p0 + min(q0 + 16, q_len);  // one past the tile's last key
+  bf16_t* orow = out + ((int64_t)b * q_len + qi) * d + h * HD;
+  if (ks >= kend) {  // wave-uniform: every query of the tile is a pad
+    if (qok) {
+#pragma unroll
+      for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+        for (int r = 0; r < 4; ++r) orow[16 * dt + 4 * g + r] = 0;
+    }
+    return;
+  }
+  auto kp = [&](int k) -> const bf16_t* { return k < p0 ? kb + (int64_t)k * HD : rows + (int64_t)(k - p0) * 3 * d + d; };
+  auto vp = [&](int k) -> const bf16_t* { return k < p0 ? vb + (int64_t)k * HD : rows + (int64_t)(k - p0) * 3 * d + 2 * d; };
+  bf16x8 qf[2];
+#pragma unroll
+  for (int kk = 0; kk < 2; ++kk) qf[kk] = *reinterpret_cast<const bf16x8*>(rows + (int64_t)qi * 3 * d + 32 * kk + 8 * g);
+  float m = -INFINITY, l = 0.f;
+  f32x4 o[4];
+#pragma unroll
+  for (int dt = 0; dt < 4; ++dt) o[dt] = f32x4{0.f, 0.f, 0.f, 0.f};
+  for (int k0 = ks; k0 < kend; k0 += 32) {
+    // the tile's V rows to LDS (4 x 16 B per lane), K fragments straight from memory
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int c = lane + 64 * i, kr = c >> 3, c8 = (c & 7) * 8;
+      *reinterpret_cast<uint4*>(vs + kr * VLD + c8) = *reinterpret_cast<const uint4*>(vp(min(k0 + kr, kend - 1)) + c8);
+    }
+    f32x4 st[2];
+#pragma unroll
+    for (int t = 0; t < 2; ++t) {
+      st[t] = f32x4{0.f, 0.f, 0.f, 0.f};
+      const bf16_t* kr = kp(min(k0 + 16 * t + qn, kend - 1));
+#pragma unroll
+      for (int kk = 0; kk < 2; ++kk) {
+        const bf16x8 kf = *reinterpret_cast<const bf16x8*>(kr + 32 * kk + 8 * g);
+        st[t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[kk], st[t], 0, 0, 0);
+      }
+    }
+    bool ok[2][4];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        ok[t][r] = qok && k0 + 16 * t + 4 * g + r <= pos;
+        mx = fmaxf(mx, ok[t][r] ? st[t][r] : -INFINITY);
+      }
+    mx = fmaxf(mx, __shfl_xor(mx, 16, 64));
+    mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
+    const float mn = fmaxf(m, mx);
+    const float sc = m == -INFINITY ? 0.f : expf(m - mn);
+    float p[2][4], sum = 0.f;
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        p[t][r] = ok[t][r] ? expf(st[t][r] - mn) : 0.f;
+        sum += p[t][r];
+      }
+    sum += __shfl_xor(sum, 16, 64);
+    sum += __shfl_xor(sum, 32, 64);
+    l = l * sc + sum;
+    m = mn;
+    bf16x8 pf;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) pf[j] = (__bf16)p[j >> 2][j & 3];
+    __syncthreads();  // the V image is written
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt) {
+      bf16x8 vf;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const bf16_t x = vs[(16 * (j >> 2) + 4 * g + (j & 3)) * VLD + 16 * dt + qn];
+        vf[j] = *reinterpret_cast<const __bf16*>(&x);
+      }
+#pragma unroll
+      for (int r = 0; r < 4; ++r) o[dt][r] *= sc;
+      o[dt] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[dt], 0, 0, 0);
+    }
+    __syncthreads();  // the V image is consumed
+  }
+  if (qok) {
+    const float inv = l > 0.f ? 1.f / l : 0.f;
+#pragma unroll
+    for (int dt = 0; dt < 4; ++dt)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) orow[16 * dt + 4 * g + r] = l > 0.f ? f2bf(o[dt][r] * inv) : (bf16_t)0;
+  }
+}
+
 }  // namespace
 
 extern "C" int kw_attention(int dtype, const void* qkv, int64_t B, int64_t H, int64_t T, int64_t hd, void* out,
@@ -2072,6 +2313,57 @@ extern "C" int kw_dec_xq_cross_fp8(const kw_dec_xq_cross_fp8_args* a, kw_stream_
                     reinterpret_cast<const bf16x8*>(a->W), a->bias, a->scale, d, p.err + 1};
   hipLaunchKernelGGL((cross_attn_row_fp8_kernel<true, ROW_NS>), dim3((unsigned)(p.n_lin + g.rows)), dim3(256), 0,
                      (hipStream_t)stream, p);
+  KW_CHECK_LAUNCH();
+  return KW_OK;
+}
+
+// (last in the file: kernel templates are emitted where they are first launched from)
+template <typename T>
+static void launch_self_attn_masked(const void* qkv, int64_t B, int64_t q_len, int64_t H, void* k_cache, void* v_cache,
+                                    int64_t t_max, const int32_t* cur_len, const int32_t* key_start, const int32_t* bp,
+                                    int64_t bp_stride, void* out, void* workspace, bool per_query, hipStream_t s) {
+  if (q_len == 1) {
+    float* part = (float*)workspace;
+    int* cnt = (int*)((char*)workspace + (size_t)(B * H) * 2 * (HD + 2) * sizeof(float));
+    dim3 grid((unsigned)(B * H), (unsigned)((t_max + 255) / 256));
+    hipLaunchKernelGGL((bp ? self_attn_step1_masked<T, true> : self_attn_step1_masked<T, false>), grid, dim3(256), 0, s,
+                       (const T*)qkv, (int)H, (T*)k_cache, (T*)v_cache, (int)t_max, cur_len, key_start, bp,
+                       (int)bp_stride, part, cnt, (T*)out);
+  } else if (sizeof(T) == 2 && !per_query) {
+    hipLaunchKernelGGL(self_attn_prefill_masked_mfma, dim3((unsigned)(B * H), (unsigned)((q_len + 15) / 16)), dim3(64), 0, s,
+                       (const bf16_t*)qkv, (int)q_len, (int)H, (bf16_t*)k_cache, (bf16_t*)v_cache, (int)t_max, cur_len,
+                       key_start, (bf16_t*)out);
+  } else {
+    hipLaunchKernelGGL(self_attn_prefill_masked<T>, dim3((unsigned)(B * H), (unsigned)q_len), dim3(256), 0, s,
+                       (const T*)qkv, (int)q_len, (int)H, (T*)k_cache, (T*)v_cache, (int)t_max, cur_len, key_start,
+                       (T*)out);
+  }
+}
+
+extern "C" int kw_self_attn_step_masked(int dtype, const void* qkv, int64_t B, int64_t q_len, int64_t H, int64_t hd,
+                                        void* k_cache, void* v_cache, int64_t t_max, const int32_t* cur_len,
+                                        const int32_t* key_start, const int32_t* bp, int64_t bp_stride, void* out,
+                                        void* workspace, size_t ws_bytes, kw_stream_t stream) {
+  if (!qkv || !k_cache || !v_cache || !cur_len || !key_start || !out || B <= 0 || q_len <= 0 || H <= 0 || t_max <= 0 ||
+      t_max > 512 || q_len > t_max)
+    return kw_set_error_msg(KW_EINVAL, "kw_self_attn_step_masked: invalid arguments (q_len <= t_max <= 512)");
+  if (hd != HD) return kw_set_error_msg(KW_EUNSUPPORTED, "kw_self_attn_step_masked: head_dim must be 64");
+  const bool per_query = (dtype & KW_SELF_ATTN_PER_QUERY) != 0;
+  dtype &= ~KW_SELF_ATTN_PER_QUERY;
+  if (dtype != KW_DT_BF16 && dtype != KW_DT_F32)
+    return kw_set_error_msg(KW_EUNSUPPORTED, "kw_self_attn_step_masked: dtype");
+  if (bp && (q_len != 1 || bp_stride < t_max))
+    return kw_set_error_msg(KW_EINVAL, "kw_self_attn_step_masked: a slot table needs q_len == 1 and bp_stride >= t_max");
+  if (q_len == 1 && (!workspace || ws_bytes < kw_self_attn_workspace(B, H, t_max)))
+    return kw_set_error_msg(KW_EINVAL,
+                            "kw_self_attn_step_masked: needs a zero-filled workspace of kw_self_attn_workspace()");
+  hipStream_t s = (hipStream_t)stream;
+  if (dtype == KW_DT_BF16)
+    launch_self_attn_masked<bf16_t>(qkv, B, q_len, H, k_cache, v_cache, t_max, cur_len, key_start, bp, bp_stride, out,
+                                    workspace, per_query, s);
+  else
+    launch_self_attn_masked<float>(qkv, B, q_len, H, k_cache, v_cache, t_max, cur_len, key_start, bp, bp_stride, out,
+                                   workspace, per_query, s);
   KW_CHECK_LAUNCH();
   return KW_OK;
 }

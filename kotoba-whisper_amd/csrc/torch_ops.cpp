@@ -216,6 +216,21 @@ void self_attn_step(const Tensor& qkv, int64_t B, int64_t q_len, int64_t H, int6
         w);
 }
 
+void self_attn_step_masked(const Tensor& qkv, int64_t B, int64_t q_len, int64_t H, int64_t hd, Tensor& k_cache,
+                           Tensor& v_cache, int64_t t_max, const Tensor& cur_len, const Tensor& key_start, Tensor& out,
+                           optional<Tensor> workspace, const optional<Tensor>& bp, int64_t flags) {
+  const char* w = "kw_self_attn_step_masked";
+  dev(qkv, w), dev(k_cache, w), dev(v_cache, w), dev(cur_len, w), dev(key_start, w), dev(out, w), dev(workspace, w), dev(bp, w);
+  TORCH_CHECK_VALUE(key_start.scalar_type() == at::kInt && key_start.is_contiguous() && key_start.numel() >= B, w,
+                    ": key_start must be a contiguous int32 tensor of B elements");
+  const size_t nb = workspace.has_value() ? (size_t)workspace->numel() * workspace->element_size() : 0;
+  c10::DeviceGuard g(qkv.device());
+  check(kw_self_attn_step_masked(dt_of(qkv) | (int)flags, ptr(qkv), B, q_len, H, hd, ptr(k_cache), ptr(v_cache), t_max,
+                                 ptr<const int32_t>(cur_len), ptr<const int32_t>(key_start), optr<const int32_t>(bp),
+                                 bp.has_value() ? bp->stride(0) : 0, ptr(out), optr<void>(workspace), nb, stream_of(qkv)),
+        w);
+}
+
 // ---- fused decode cross-attention query + step -----------------------------------------------------------
 // dims = [ldx, M, d, H, S]
 void dec_xq_cross(const Tensor& x, const Tensor& W, const optional<Tensor>& bias, const Tensor& ln_colsum,
@@ -659,6 +674,8 @@ TORCH_LIBRARY(kw, m) {
         "Tensor(b!)? hb, int flags=0) -> ()");
   m.def("self_attn_step(Tensor qkv, int B, int q_len, int H, int hd, Tensor(a!) k_cache, Tensor(b!) v_cache, "
         "int t_max, Tensor cur_len, Tensor(c!) out, Tensor(d!)? workspace, Tensor? bp) -> ()");
+  m.def("self_attn_step_masked(Tensor qkv, int B, int q_len, int H, int hd, Tensor(a!) k_cache, Tensor(b!) v_cache, "
+        "int t_max, Tensor cur_len, Tensor key_start, Tensor(c!) out, Tensor(d!)? workspace, Tensor? bp, int flags=0) -> ()");
   m.def("dec_qkv_self(Tensor x, Tensor W, Tensor? bias, Tensor ln_colsum, Tensor(a!) k_cache, Tensor(b!) v_cache, "
         "Tensor cur_len, Tensor(c!) out, Tensor(d!) workspace, int[] dims, float ln_eps, float scale) -> ()");
   m.def("dec_xq_cross(Tensor x, Tensor W, Tensor? bias, Tensor ln_colsum, Tensor k, Tensor v, Tensor(a!) out, "
@@ -703,6 +720,7 @@ TORCH_LIBRARY_IMPL(kw, CUDA, m) {
   m.impl("attention", &attention);
   m.impl("embed", &embed);
   m.impl("self_attn_step", &self_attn_step);
+  m.impl("self_attn_step_masked", &self_attn_step_masked);
   m.impl("cross_attn_step", &cross_attn_step);
   m.impl("dec_qkv_self", &dec_qkv_self);
   m.impl("dec_xq_cross", &dec_xq_cross);

@@ -73,6 +73,10 @@ class DecodeSession:
         # beam search: cache row holding position p of row r's history (beams share a prefix)
         self.bp = torch.zeros((R, T_MAX), device=dev, dtype=torch.int32) if beams > 1 else None
         self.cur_len = torch.zeros((1,), device=dev, dtype=torch.int32)
+        # per-row first key of a left-padded pass (kw_self_attn_step_masked); allocated once: the masked plans and
+        # their captured graphs hold its address, generate(key_start=...) fills it per pass
+        self.key_start = torch.zeros((R,), device=dev, dtype=torch.int32)
+        self._long_q = []  # the long prefill lengths whose buffers are alive, least recently used first
         self.unfinished = torch.ones((R,), device=dev, dtype=torch.int32)
         self.counter = torch.zeros((1,), device=dev, dtype=torch.int32)
         self.n_unfinished = torch.zeros((1,), device=dev, dtype=torch.int32)
@@ -147,6 +151,7 @@ class DecodeSession:
         v.cross, v.kc, v.vc = self.cross[:, r0:r1], self.kc[:, r0:r1], self.vc[:, r0:r1]
         v.fp8, v.cross_scale = self.fp8, self.cross_scale[:, r0:r1] if self.fp8 else None
         v.ids, v.bp, v.cur_len, v.logits = self.ids[r0:r1], None, self.cur_len, self.logits[r0:r1]
+        v.key_start, v._long_q = self.key_start[r0:r1], None  # (a view's long prefill sizes go with its parent's)
         v._bufs, v._plans, v._align_logs = {}, {}, {}
         v.lin_ws = torch.zeros_like(self.lin_ws) if self.lin_ws is not None else None
         v.self_ws = torch.zeros_like(self.self_ws)
@@ -168,15 +173,15 @@ class DecodeSession:
             self._plans[key] = (views, [L.new_stream(self.eng.device, owner=self) for _ in range(parts)])
         return self._plans[key]
 
-    def _run_prefill(self, P: int, parts: int) -> None:
+    def _run_prefill(self, P: int, parts: int, masked: bool = False) -> None:
         """The prompt's forward pass (prefill) as ``parts`` row blocks on side streams, their launches issued in
         lockstep: each block's kernels are latency-bound chains on few CUs, and two of them overlap (the
         encoder's split, engine._encode_split).  Joined on the current stream before the sampler."""
         if parts <= 1 or self.nb != 1 or self.R < 2 * parts:
-            self._run(self._step_plans(P))
+            self._run(self._step_plans(P, masked=masked))
             return
         views, streams = self._prefill_parts(parts)
-        seqs = [v._step_plans(P) for v in views]
+        seqs = [v._step_plans(P, masked=masked) for v in views]
         cur = torch.cuda.current_stream(self.eng.device)
         for st in streams:
             st.wait_stream(cur)
@@ -187,8 +192,42 @@ class DecodeSession:
         for st in streams:
             cur.wait_stream(st)
 
+    # Prompts of a few tokens keep one buffer set per length, as ever.  A conditioned pass has a prompt of up to
+    # ~228 tokens whose length changes from pass to pass: of those long lengths at most LONG_KEEP stay alive, and a
+    # length that leaves takes its plans, its row views' buffers and the configurations whose captured prefill
+    # graphs hold its addresses with it -- prefill memory does not grow with the number of lengths seen.
+    # Lengths leave only outside a graph capture (generate() and teacher_forced_logits() call _keep_prefill before
+    # they capture or run): a dropped configuration destroys its hipGraphs, which is an error inside a capture.
+    LONG_Q, LONG_KEEP = 8, 2
+
+    def _keep_prefill(self, q: int) -> None:
+        """Mark the long prefill length ``q`` as the most recently used and drop the lengths beyond LONG_KEEP."""
+        if q <= self.LONG_Q or self._long_q is None:
+            return
+        if q in self._long_q:
+            self._long_q.remove(q)
+        self._long_q.append(q)
+        while len(self._long_q) > self.LONG_KEEP:
+            self._drop_prefill(self._long_q.pop(0))
+
+    def _drop_prefill(self, q: int) -> None:
+        self._bufs.pop(q, None)
+        for k in [k for k in self._plans if k[0] == q]:
+            del self._plans[k]
+        for k in [k for k, c in self._greedy_cfg.items() if c["P"] == q]:
+            del self._greedy_cfg[k]
+        for k, (views, _) in [(k, v) for k, v in self._plans.items() if k[0] == "views"]:
+            for v in views:
+                v._bufs.pop(q, None)
+                for kk in [kk for kk in v._plans if kk[0] == q]:
+                    del v._plans[kk]
+
     def _buffers(self, q: int):
         if q not in self._bufs:
+            if q > self.LONG_Q and self._long_q is not None and q not in self._long_q:
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("a long prefill length must be registered (_keep_prefill) before a capture")
+                self._keep_prefill(q)
             s, dev, dt = self.eng.shape, self.eng.device, self.eng.dtype
             d, rows = s.d_model, self.R * q
             self._bufs[q] = dict(
@@ -226,15 +265,22 @@ class DecodeSession:
                                                         dtype=self.eng.dtype)
         return log
 
-    def _step_plans(self, q: int, fused: bool = False, align=None, begin_index: int = 0):
+    def _step_plans(self, q: int, fused: bool = False, align=None, begin_index: int = 0, masked: bool = False):
         """The decoder forward for q new positions per row (q = prompt length for the prefill, 1 after).
         ``align`` (q == 1, greedy): the alignment (layer, head) pairs whose cross-attention queries every step logs
         (kw_align_capture after the layer's query projection; such a layer takes the two-launch cross path, which
         leaves the query in global memory and is bitwise the fused block).  None: exactly the plain plan.
         ``fused`` (q == 1): each layer's LayerNorm-fused QKV projection and self-attention step as ONE
-        kw_dec_qkv_self launch (caches bitwise the two-launch plan's, attention within bf16 rounding) -- for steps at positions < 256 only."""
-        fused = bool(fused and q == 1 and self.qs_ok)
+        kw_dec_qkv_self launch (caches bitwise the two-launch plan's, attention within bf16 rounding) -- for steps at positions < 256 only.
+        ``masked``: the self-attention items call kw_self_attn_step_masked with this session's ``key_start`` (a
+        left-padded pass); there is no masked fused block, so ``fused`` is off."""
+        fused = bool(fused and q == 1 and self.qs_ok and not masked)
         key = (q, fused) if align is None else (q, fused, align, begin_index)
+        if masked:
+            if align is not None:
+                raise NotImplementedError("token timestamps with a per-row key_start")
+            key = (q, fused, "masked")
+        self_kind = "self_masked" if masked else "self"
         if key in self._plans:
             return self._plans[key]
         eng, s = self.eng, self.eng.shape
@@ -268,7 +314,7 @@ class DecodeSession:
                 else:
                     seq.append(lin(hb, lay["qkv_w"], rows, 3 * d, d, ln=(eps, lay["qkv_cs"]), bias=lay["qkv_b"],
                                    C=b["qkv"], scale=scale, scale_cols=d, workspace=ws, tag="qkv", ldx=xld))
-                    seq.append(("self", q, b["qkv"], li, b["attn"]))
+                    seq.append((self_kind, q, b["qkv"], li, b["attn"]))
                 seq.append(lin(b["attn"], lay["o_w"], rows, d, d, bias=lay["o_b"], resid=(h, hb, d, 0), workspace=ws,
                                tag="o", hb_tiled=tiled, ldx=xld if fused else None))  # (the fused block's attn)
                 xc = q == 1 and self.xc_ok and li not in capture
@@ -303,7 +349,7 @@ class DecodeSession:
             seq.append(("ln", b["h"], lay["ln1_g"], lay["ln1_b"], b["x"]))
             seq += self._gemm(b["x"], lay["qkv_w"], b["qkv"], rows, 3 * d, d, bias=lay["qkv_b"], scale=scale,
                               scale_cols=d)
-            seq.append(("self", q, b["qkv"], li, b["attn"]))
+            seq.append((self_kind, q, b["qkv"], li, b["attn"]))
             seq += self._gemm(b["attn"], lay["o_w"], b["h"], rows, d, d, bias=lay["o_b"], epilogue=L.KW_EPI_RESID)
             seq.append(("ln", b["h"], lay["ln2_g"], lay["ln2_b"], b["x"]))
             seq += self._gemm(b["x"], lay["xq_w"], b["qx"], rows, d, d, bias=lay["xq_b"], scale=scale, scale_cols=d)
@@ -339,6 +385,10 @@ class DecodeSession:
                 _, q, qkv, li, out = p
                 ops.self_attn_step(qkv, B, q, H, _HD, self.kc[li], self.vc[li], T_MAX, self.cur_len, out, self.self_ws,
                                    bp=self.bp if q == 1 else None)
+            elif k == "self_masked":
+                _, q, qkv, li, out = p
+                ops.self_attn_step_masked(qkv, B, q, H, _HD, self.kc[li], self.vc[li], T_MAX, self.cur_len, self.key_start,
+                                          out, self.self_ws, bp=self.bp if q == 1 else None)
             elif k == "cross":  # rows b*nb*q + (beam*q + i) attend to item b's K/V
                 _, q, qx, li, out, ws = p
                 if self.fp8:
@@ -389,18 +439,35 @@ class DecodeSession:
         self._run(self._step_plans(P))
         return self.logits
 
-    def teacher_forced_logits(self, seq: torch.Tensor, P: int) -> torch.Tensor:
+    def _set_key_start(self, key_start) -> bool:
+        """Fill the ``key_start`` buffer for a pass; False (buffer untouched, today's plans) for None or all zero."""
+        if key_start is None:
+            return False
+        ks = np.asarray(key_start, dtype=np.int64).reshape(-1)
+        if ks.shape != (self.B,) or (ks < 0).any() or (ks > T_MAX).any():
+            raise ValueError(f"key_start must hold one value in [0, {T_MAX}] per row")
+        if not ks.any():
+            return False
+        if self.nb != 1:
+            raise NotImplementedError("a per-row key_start with beam search")
+        self.key_start.copy_(torch.from_numpy(ks.astype(np.int32)))
+        return True
+
+    def teacher_forced_logits(self, seq: torch.Tensor, P: int, key_start=None) -> torch.Tensor:
         """Raw logits (B, T-P+1, V) predicting seq[:, P:] and one more, feeding the reference tokens
-        (validation utility: compares the decoder step with a reference's per-step logits)."""
+        (validation utility: compares the decoder step with a reference's per-step logits).  ``key_start``: per
+        row, the first key position attended (a left-padded prompt); None or zeros: the unmasked plans."""
+        masked = self._set_key_start(key_start)
+        self._keep_prefill(P)
         B, T = seq.shape
         seq = seq.to(self.eng.device)
         self.ids.zero_()
         self.ids[:, :T].copy_(seq)
         self.cur_len.fill_(P)
         out = []
-        self._run(self._step_plans(P))
+        self._run(self._step_plans(P, masked=masked))
         out.append(self.logits.clone())
-        step = self._step_plans(1, fused=T <= 256)
+        step = self._step_plans(1, fused=T <= 256, masked=masked)
         for t in range(P, T):
             self.cur_len.fill_(t + 1)
             self._run(step)
@@ -432,7 +499,7 @@ class DecodeSession:
 
     def generate(self, prompt: torch.Tensor, gen, *, max_length: int, return_timestamps: bool,
                  check_every: int = 4, use_graph: bool = True, record_scores: bool = False, align=None,
-                 num_frames=None, median_filter_width: int = 7, sample=None):
+                 num_frames=None, median_filter_width: int = 7, sample=None, key_start=None):
         """Greedy loop of GenerationMixin._sample (TF/generation/utils.py:2783-2941).
 
         ``sample``: None (the greedy path, unchanged), or a dict -- ``temperature`` (0 = argmax), ``seed``, ``attempt``
@@ -450,7 +517,16 @@ class DecodeSession:
         heads' cross-attention queries, and after decoding the alignment stage (weights, normalisation, DTW) runs
         on device over the steps the reference would have run; ``self.align_out["frames"]`` holds int32 (B, L - P - 1),
         the encoder position of every step (``num_frames``: per-row feature frames, the crop of
-        TF generation_whisper.py:310-354, or None)."""
+        TF generation_whisper.py:310-354, or None).
+
+        ``key_start``: per row, the number of leading pad positions of a left-padded ``prompt`` (the
+        decoder_attention_mask of a conditioned pass, TF generation_whisper.py:1908): the row attends keys from there
+        on, positions stay the plain arange.  None or all zero: exactly the unmasked plans and graphs.  Otherwise the
+        self-attention runs kw_self_attn_step_masked in the prefill and in every step (never the fused self block)."""
+        masked = self._set_key_start(key_start)
+        self._keep_prefill(prompt.shape[1])
+        if masked and align is not None:
+            raise NotImplementedError("token timestamps with a per-row key_start")
         if align is not None:
             align = tuple((int(l), int(h)) for l, h in align)
             nl, nh = self.eng.shape.decoder_layers, self.eng.H
@@ -500,6 +576,8 @@ class DecodeSession:
                self.eng.prefill_streams, self.eng.fuse_lm_greedy, align, "fp8_e4m3" if self.fp8 else None)
         if sample is not None:
             key += ("sample",)
+        if masked:
+            key += ("masked",)
         cfg = self._greedy_cfg.get(key)
         if cfg is None:
             sup = torch.zeros((self.eng.shape.vocab_size,), dtype=torch.uint8)
@@ -521,7 +599,7 @@ class DecodeSession:
                 sampler = ops.SamplerPlan(self.logits, sup, bsup if nb else None, self.ids, self.cur_len,
                                           self.unfinished, self.counter, self.n_unfinished, scores_out=score_buf,
                                           workspace=self.samp_ws, **pcfg)
-            cfg = dict(sampler=sampler, score_buf=score_buf, graph=None)
+            cfg = dict(sampler=sampler, score_buf=score_buf, graph=None, P=P)
             if len(self._greedy_cfg) >= 8:  # bound the cache (each entry may hold a graph)
                 self._greedy_cfg.pop(next(iter(self._greedy_cfg)))
             self._greedy_cfg[key] = cfg
@@ -530,7 +608,7 @@ class DecodeSession:
         # prefill (replayed from a graph cached with the configuration: ~260 launches otherwise go
         # through Python one by one)
         def prefill():
-            self._run_prefill(P, self.eng.prefill_streams)
+            self._run_prefill(P, self.eng.prefill_streams, masked)
             sampler()
 
         pg = cfg.get("prefill_graph")
@@ -547,8 +625,8 @@ class DecodeSession:
         n_steps = max_length - P  # tokens the reference can add at most
         done = 1
         fused = max_length <= 256  # every step's position < 256 (kw_dec_qkv_self's key range)
-        step_seq = self._step_plans(1, fused=fused, align=align, begin_index=P)
-        self.fused_last = bool(fused and self.qs_ok)
+        step_seq = self._step_plans(1, fused=fused, align=align, begin_index=P, masked=masked)
+        self.fused_last = bool(fused and self.qs_ok and not masked)
         # the step's LM head + greedy step as one launch (kw_dec_lm_greedy; no timestamps, no recorded scores)
         tail = sampler
         s = self.eng.shape
@@ -739,7 +817,7 @@ class DecodeSession:
                                     max_initial_ts=gen.max_initial_timestamp_index, begin_index=P,
                                     max_length=max_length, fill_id=fill, length_penalty=length_penalty,
                                     early_stopping=early_stopping)
-            cfg = dict(st=st, step=step, graph=None, prefill_graph=None)
+            cfg = dict(st=st, step=step, graph=None, prefill_graph=None, P=P)
             if len(self._greedy_cfg) >= 8:
                 self._greedy_cfg.pop(next(iter(self._greedy_cfg)))
             self._greedy_cfg[key] = cfg

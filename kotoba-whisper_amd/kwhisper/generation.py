@@ -20,6 +20,10 @@ TF/models/whisper/generation_whisper.py:383-968):
     ``logprob_threshold``, ``no_speech_threshold``: per seek pass the attempt loop of ``generate_with_fallback``, every
     row's ``_need_fallback`` decision, the no-speech skip; tokens drawn and log-probabilities accumulated on device
     (kw_sample_step, csrc/sampling.hip)                               :970-1116, :1243-1287, :876-881, :1949-1974
+  * ``prompt_ids`` / ``prompt_condition_type`` / ``condition_on_prev_tokens``: per seek pass the decoder input of
+    ``_prepare_decoder_input_ids`` -- the previous text behind ``<|startofprev|>``, left-padded to the pass's longest
+    row -- built on the host (``build_pass_input``); the pads are masked in the decoder self-attention by a per-row
+    first key (kw_self_attn_step_masked), positions stay the plain arange     :1853-1918, :126-235, :1119-1126, :905-915
 
 Deliberate differences of the fallback from transformers 5.15.0:
   * ``no_speech_threshold`` without ``logprob_threshold`` raises ``ValueError`` (the reference dies on an unbound local);
@@ -30,7 +34,10 @@ Deliberate differences of the fallback from transformers 5.15.0:
   * a row's tokens are counted up to and including its first EOS; the reference counts pad tokens anywhere in the row
     when it strips the padding (:1063-1071), which differs only for a padded row that also sampled the pad token;
   * sampled tokens come from the engine's own counter-based generator (``manual_seed``), so they are distributed as
-    the reference's (softmax(s / T), multinomial) but are not the same draws as torch's.
+    the reference's (softmax(s / T), multinomial) but are not the same draws as torch's;
+  * ``do_condition_on_prev_tokens`` after a fallback attempt is kept per audio; the reference writes it at the row's
+    position in the pass's batch (:1091) and reads it by the audio's index (:1884), which differ once an audio has left
+    the batch.
 """
 from __future__ import annotations
 
@@ -207,7 +214,7 @@ class KWhisperForConditionalGeneration:
             )
         if logits_processor or stopping_criteria:
             raise NotImplementedError("custom logits_processor / stopping_criteria are not supported on device")
-        for k in ("prompt_ids", "prefix_allowed_tokens_fn", "assistant_model", "output_scores"):
+        for k in ("prefix_allowed_tokens_fn", "assistant_model", "output_scores"):
             if kwargs.get(k) is not None and kwargs.get(k) is not False:
                 raise NotImplementedError(f"`{k}` is not supported by the MI355X engine yet")
         if kwargs.get("num_return_sequences") not in (None, 1):
@@ -224,8 +231,24 @@ class KWhisperForConditionalGeneration:
         cond_prev = kwargs.get("condition_on_prev_tokens")
         if cond_prev is None:
             cond_prev = getattr(gen, "condition_on_prev_tokens", None)
-        if cond_prev:
-            raise NotImplementedError("`condition_on_prev_tokens=True` is not supported by the MI355X engine yet")
+        gen.condition_on_prev_tokens = cond_prev
+        # _set_prompt_condition_type (generation_whisper.py:1732-1748)
+        prompt_condition_type = kwargs.get("prompt_condition_type") or "first-segment"
+        if prompt_condition_type not in ("first-segment", "all-segments"):
+            raise ValueError(
+                f"`prompt_condition_type={prompt_condition_type} does not exist. Make sure to set "
+                "`prompt_condition_type` to one of first-segment, all-segments")
+        if cond_prev is not True and prompt_condition_type == "all-segments":
+            raise ValueError(
+                "Make sure to set `condition_on_prev_tokens=True` when setting `prompt_condition_type='all-segments'`.")
+        cond_prev = bool(cond_prev)
+        prompt_ids = kwargs.get("prompt_ids")
+        if prompt_ids is not None:
+            prompt_ids = (prompt_ids.detach().cpu().numpy() if isinstance(prompt_ids, torch.Tensor)
+                          else np.asarray(prompt_ids)).astype(np.int64)
+            if prompt_ids.ndim != 1 or prompt_ids.size == 0:
+                raise ValueError("`prompt_ids` must be a non-empty rank-1 tensor of token ids")
+        prompted = prompt_ids is not None or cond_prev
         temperature = kwargs.get("temperature")
         temperatures = list(temperature) if isinstance(temperature, (list, tuple)) else [temperature]
         has_thr = any(v is not None for v in thr.values())
@@ -243,6 +266,14 @@ class KWhisperForConditionalGeneration:
             if kwargs.get("return_token_timestamps"):
                 raise NotImplementedError("the decoding fallback (thresholds or a temperature above 0) with "
                                           "`return_token_timestamps` is not supported by the MI355X engine yet")
+        if prompted:
+            if num_beams > 1:
+                raise NotImplementedError("`prompt_ids` / `condition_on_prev_tokens` with `num_beams` > 1 is not "
+                                          "supported by the MI355X engine yet; use num_beams=1")
+            if kwargs.get("return_token_timestamps"):
+                raise NotImplementedError("`prompt_ids` / `condition_on_prev_tokens` with `return_token_timestamps` is "
+                                          "not supported by the MI355X engine yet (the alignment log is not extended to "
+                                          "padded prompts)")
         if num_beams > 8:
             raise NotImplementedError("num_beams > 8 is not supported by the device beam search")
         if getattr(self.engine, "cross_kv_fp8", False):
@@ -288,6 +319,11 @@ class KWhisperForConditionalGeneration:
             feats = None
         nseg = s.n_frames
         shortform = total <= nseg
+        if prompted and fallback and shortform:
+            raise NotImplementedError("`prompt_ids` / `condition_on_prev_tokens` together with the decoding fallback "
+                                      "(thresholds or a temperature above 0) is supported for long-form input (more than "
+                                      "one 30 s window) only; it is not supported for short-form input by the MI355X "
+                                      "engine yet")
         if return_timestamps is None:
             return_timestamps = bool(getattr(gen, "return_timestamps", False))
         if not shortform:
@@ -309,7 +345,7 @@ class KWhisperForConditionalGeneration:
         prompt_all = self._init_tokens(gen, B, language, task, return_timestamps, feats, enc_given)
         P = prompt_all.shape[1]
 
-        if max_new_tokens is not None and max_new_tokens + P > s.max_target_positions:
+        if not prompted and max_new_tokens is not None and max_new_tokens + P > s.max_target_positions:
             raise ValueError(
                 f"The length of `decoder_input_ids`, including special start tokens, prompt tokens, and previous "
                 f"tokens, is {P},  and `max_new_tokens` is {max_new_tokens}. Thus, the combined length of "
@@ -327,7 +363,15 @@ class KWhisperForConditionalGeneration:
             max_frames = np.full(B, total, dtype=np.int64)
         seek = np.zeros(B, dtype=np.int64)
         ts_begin = gen.timestamp_begin
-        segments = [[] for _ in range(B)]
+        # _prepare_segments (:1119-1126): "first-segment" seeds every row's segments with the prompt's text
+        first_seg = prompt_ids is not None and prompt_condition_type == "first-segment"
+        if first_seg:
+            seed = prompt_ids[1:] if prompt_ids[0] == gen.prev_sot_token_id else prompt_ids
+            segments = [[{"tokens": seed}] for _ in range(B)]
+        else:
+            segments = [[] for _ in range(B)]
+        do_condition = [cond_prev] * B  # per audio, for its next pass (_expand_variables_for_generation :1304)
+        pass_P, pass_key_start, pass_prompt = [], [], []
         batch_map = list(range(B))
         last_ids = None
         passes = 0
@@ -366,6 +410,25 @@ class KWhisperForConditionalGeneration:
                 enc = eh.to(eng.device, eng.dtype).reshape(B * s.max_source_positions, s.d_model).contiguous()
                 enc_key = None
             prompt = prompt_all[batch_map]
+            key_start = None
+            if prompted:
+                # this pass's decoder input and per-row first key; the same for every attempt of the fallback
+                prompt, key_start = build_pass_input(prompt_all, segments, batch_map, do_condition, prompt_ids, gen,
+                                                     s.max_target_positions, prompt_condition_type)
+                P = prompt.shape[1]
+                # _set_max_new_tokens_and_length (:1920-1945), with this pass's length
+                if (max_new_tokens or 0) + P > s.max_target_positions:
+                    raise ValueError(
+                        f"The length of `decoder_input_ids`, including special start tokens, prompt tokens, and previous "
+                        f"tokens, is {P},  and `max_new_tokens` is {max_new_tokens or 0}. Thus, the combined length of "
+                        f"`decoder_input_ids` and `max_new_tokens` is: {(max_new_tokens or 0) + P}. This exceeds the "
+                        f"`max_target_positions` of the Whisper model: {s.max_target_positions}. You should either reduce "
+                        "the length of your prompt, or reduce the value of `max_new_tokens`, so that their combined length "
+                        f"is less than {s.max_target_positions}.")
+            pass_P.append(int(P))
+            pass_key_start.append(None if key_start is None else [int(k) for k in key_start])
+            if self.record_pass_ids:
+                pass_prompt.append((np.asarray(prompt).copy(), list(do_condition)))
             if max_new_tokens is None:
                 max_length = min(max_length + min(s.max_target_positions // 2 - 1, P), s.max_target_positions)
                 eff_max = max_length
@@ -380,8 +443,11 @@ class KWhisperForConditionalGeneration:
                         and self._sot_logits.shape[0] == cur:
                     sot = self._sot_logits  # language detection ran this very position on these features
                 ids, skip, attempts = self._generate_with_fallback(sess, prompt, gen, eff_max, return_timestamps,
-                                                                   temperatures, thr, batch_map, sot)
+                                                                   temperatures, thr, batch_map, sot, key_start)
                 fallback_log.append(attempts)
+                for rec in attempts:  # (:1088-1093): a row accepted at a temperature of 0.5 or more loses its conditioning
+                    for p in rec["rows"]:
+                        do_condition[p] = cond_prev and rec["temperature"] < 0.5
             elif num_beams > 1:
                 ids = sess.generate_beam(torch.from_numpy(prompt), gen, num_beams=num_beams, max_length=eff_max,
                                          return_timestamps=return_timestamps, length_penalty=length_penalty,
@@ -398,7 +464,7 @@ class KWhisperForConditionalGeneration:
                     align_log.append(dict(sess.align_out, rows=[int(p) for p in batch_map], num_input_ids=P))
             else:
                 ids = sess.generate(torch.from_numpy(prompt), gen, max_length=eff_max,
-                                    return_timestamps=return_timestamps)
+                                    return_timestamps=return_timestamps, key_start=key_start)
             passes += 1
             last_ids = ids
             pass_log.append(([int(p) for p in batch_map], [int(seek[p]) for p in batch_map],
@@ -417,9 +483,13 @@ class KWhisperForConditionalGeneration:
                 segments[p] += segs
             if token_ts:
                 last_ts = pass_ts
-        self.stats = {"passes": passes, "row_passes": row_passes, "pass_log": pass_log}
+        if first_seg:  # the seeded prompt is no part of the result (:905-915)
+            segments = [x[1:] for x in segments]
+        self.stats = {"passes": passes, "row_passes": row_passes, "pass_log": pass_log, "pass_P": pass_P,
+                      "pass_key_start": pass_key_start}
         if self.record_pass_ids:
             self.stats["pass_ids"] = pass_ids
+            self.stats["pass_prompt"] = pass_prompt
         if token_ts and self.record_alignment:
             self.stats["alignment"] = align_log
         if fallback:
@@ -448,7 +518,7 @@ class KWhisperForConditionalGeneration:
         return res
 
     def _generate_with_fallback(self, sess, prompt, gen, max_length, return_timestamps, temperatures, thr, batch_map,
-                                sot_logits=None):
+                                sot_logits=None, key_start=None):
         """One seek pass's attempt loop (``generate_with_fallback``, generation_whisper.py:1001-1116): decode at each
         temperature of the schedule in turn -- 0 greedy, above 0 sampled -- re-decoding only the rows whose
         ``_need_fallback`` decision asks for it, in the same session (its cross K/V stays; no re-encode); the last
@@ -469,6 +539,7 @@ class KWhisperForConditionalGeneration:
             active = np.zeros(cur, bool)
             active[rows] = True
             ids = sess.generate(torch.from_numpy(prompt), gen, max_length=max_length, return_timestamps=return_timestamps,
+                                **({} if key_start is None else {"key_start": key_start}),
                                 sample=dict(temperature=t, seed=self._seed, active=active,
                                             attempt=(self._lane << 24) | (self._attempts & 0xFFFFFF)))
             rec = dict(rows=[int(batch_map[i]) for i in rows], temperature=float(t), avg_logprob=[], compression_ratio=[],
@@ -579,6 +650,55 @@ class KWhisperForConditionalGeneration:
                 r.pop()
         arr = np.asarray(rows, dtype=np.int64)
         return np.broadcast_to(arr, (B, arr.shape[1])).copy()
+
+
+def build_pass_input(init_tokens, segments, batch_map, do_condition, prompt_ids, gen, max_target_positions,
+                     prompt_condition_type="first-segment"):
+    """One seek pass's ``decoder_input_ids`` and per-row first key, in numpy: ``_prepare_decoder_input_ids``
+    (generation_whisper.py:1853-1918) with the left-padding ``_pad_to_max_length`` (:126-235).
+
+    ``init_tokens`` (B, n) int64; ``segments``: per audio, its segments so far (dicts with ``tokens``; with
+    "first-segment" the first one is the prompt's text); ``batch_map``: the audios still running, in row order;
+    ``do_condition``: per audio, whether its next pass sees its previous text; ``prompt_ids``: rank-1 or None.
+    Returns (ids (rows, P) int64, key_start): key_start[r] is the number of leading positions of row r equal to
+    ``pad_token_id`` -- the mask is ``ids != pad_token_id`` as at :1908 -- or None where the reference passes no mask.
+    """
+    ids = np.asarray(init_tokens, dtype=np.int64)[list(batch_map)]
+    pad = gen.pad_token_id
+    prev_sot = getattr(gen, "prev_sot_token_id", None)
+    if prev_sot is None and gen.suppress_tokens is not None and len(gen.suppress_tokens) >= 2:
+        prev_sot = gen.suppress_tokens[-2]
+    if any(do_condition) and len(segments[0]) > 0:
+        cut = max_target_positions // 2 - 1
+        if prompt_ids is not None and prompt_condition_type == "all-segments":
+            bos = np.asarray(prompt_ids, dtype=np.int64)
+        else:
+            bos = np.asarray([prev_sot], dtype=np.int64) if prev_sot is not None else None
+        rows = []
+        for p in batch_map:
+            segs = segments[p] if do_condition[p] else None
+            if segs is not None and len(segs) > 0:
+                # a segment that ends with two timestamps gives only the first of them (skip_ending_double_timestamps)
+                toks = [np.asarray(g["tokens"], dtype=np.int64) for g in segs]
+                toks = [t[:-1] if len(t) > 2 and t[-2] >= gen.timestamp_begin else t for t in toks]
+                row = np.concatenate(toks)[-cut:]
+                if bos is not None:
+                    row = np.concatenate([bos, row])
+            else:
+                row = bos if bos is not None else np.zeros(0, np.int64)
+            rows.append(row)
+        longest = max(len(r) for r in rows)
+        prev = np.full((len(rows), longest), pad, dtype=np.int64)
+        for r, row in enumerate(rows):
+            prev[r, longest - len(row):] = row
+        ids = np.concatenate([prev, ids], axis=1)
+        keep = ids != pad
+        key_start = np.where(keep.any(1), keep.argmax(1), ids.shape[1]).astype(np.int64)
+        return ids, key_start
+    if prompt_ids is not None:
+        ids = np.concatenate([np.broadcast_to(np.asarray(prompt_ids, dtype=np.int64), (ids.shape[0], len(prompt_ids))),
+                              ids], axis=1)
+    return ids, None
 
 
 def _strip_pass_row(seq, pad, eos, keep_eos=False):

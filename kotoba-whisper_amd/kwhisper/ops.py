@@ -364,6 +364,28 @@ def self_attn_step(qkv, B, q_len, H, hd, k_cache, v_cache, t_max, cur_len, out, 
                                      _p(workspace), nb, _s()), "kw_self_attn_step")
 
 
+KW_SELF_ATTN_PER_QUERY = 0x100
+
+
+def self_attn_step_masked(qkv, B, q_len, H, hd, k_cache, v_cache, t_max, cur_len, key_start, out, workspace=None,
+                          bp=None, per_query=False):
+    """``self_attn_step`` with a per-row first key: row b attends key positions [key_start[b], own position]
+    (``key_start``: [B] int32; the keys below are never read; a query below its row's key_start gives zeros).
+    ``per_query``: the bf16 prefill by the per-query kernel (the f32 form) instead of the MFMA tile kernel."""
+    flags = KW_SELF_ATTN_PER_QUERY if per_query else 0
+    _cuda(qkv, k_cache, v_cache, cur_len, key_start, out, workspace, bp)
+    if key_start.dtype != torch.int32 or key_start.numel() < B or not key_start.is_contiguous():
+        raise ValueError("kw_self_attn_step_masked: key_start must be a contiguous int32 tensor of B elements")
+    if _BACKEND == "torch":
+        _kw().self_attn_step_masked(qkv, B, q_len, H, hd, k_cache, v_cache, t_max, cur_len, key_start, out, workspace, bp,
+                                    flags)
+        return
+    nb = workspace.numel() * workspace.element_size() if workspace is not None else 0
+    L.check(_lib().kw_self_attn_step_masked(_dt(qkv) | flags, _p(qkv), B, q_len, H, hd, _p(k_cache), _p(v_cache), t_max,
+                                            _p(cur_len), _p(key_start), _p(bp), bp.stride(0) if bp is not None else 0,
+                                            _p(out), _p(workspace), nb, _s()), "kw_self_attn_step_masked")
+
+
 def qkv_self_workspace_bytes(M, d) -> int:
     return _ws_bytes("qkv_self", M, d)
 
