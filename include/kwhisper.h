@@ -594,6 +594,37 @@ int kw_dtw(const float* matrix, int64_t B, int64_t T, int64_t S, const int32_t* 
            size_t ws_bytes, kw_stream_t stream);
 size_t kw_dtw_workspace(int64_t B, int64_t T, int64_t S);
 
+/* ---- repetition_penalty / no_repeat_ngram_size (additive, ABI 112 unchanged) -------------------------
+ * GenerationMixin's RepetitionPenaltyLogitsProcessor followed by NoRepeatNGramLogitsProcessor (TF generation/
+ * logits_process.py:406-413, 1121-1139), which run BEFORE the Whisper processors (TF generation/utils.py:1174-1183,
+ * merge at :1293).  Both read a row's whole history ids[r][0 .. L), L = *cur_len (a DEVICE scalar read by the launch,
+ * so a captured step replays): forced tokens, a conditioned pass's previous text and its left pads included.
+ *   penalty: every token v that occurs in the history gets s[v] = s[v] < 0 ? s[v] * penalty : s[v] / penalty -- f32,
+ *            a true IEEE division, computed once from the original s[v] however often v occurs (NaN, -0.0 and +-inf
+ *            take what that expression gives).  1.0 = off.
+ *   ngram:   n > 0: with L >= n, for every window ids[i .. i+n) with i + n <= L whose first n-1 tokens equal the
+ *            history's last n-1 tokens, s[window's last token] = -inf (n = 1 bans every token of the history; a token
+ *            both penalised and banned ends as -inf).  0 = off.
+ * History ids outside [0, V) are skipped, never dereferenced.  penalty <= 0 or not finite, ngram < 0 or a NULL pointer:
+ * KW_EINVAL, nothing is launched. */
+
+/* In place on f32 scores [R][V], one workgroup per row: the greedy and sampled tails run it on the raw logits between
+ * the LM head and kw_greedy_step / kw_sample_step.  No workspace.  ids: [R][ids_stride] int64, ids_stride <= 4096
+ * (KW_EUNSUPPORTED beyond: a thread holds its history positions' original scores in registers until every thread of
+ * the row has read its own).  penalty == 1.0 && ngram == 0 leaves the buffer untouched (nothing is launched). */
+int kw_repeat_process(float* scores, int64_t R, int64_t V, const int64_t* ids, int64_t ids_stride,
+                      const int32_t* cur_len, float penalty, int32_t ngram, kw_stream_t stream);
+
+/* kw_beam_logprobs with the two processors applied to every element's log-prob -- computed exactly as
+ * kw_beam_logprobs computes it, (x - max) - log(sum exp(x - max)), and not renormalised afterwards (TF generation/
+ * utils.py:3380-3381) -- before the Whisper processors and the timestamp mass rule.  Arguments, workspace, done and k
+ * as kw_beam_logprobs.  V <= 65536 (two vocabulary bitsets per workgroup; KW_EUNSUPPORTED beyond).  With
+ * penalty == 1.0 && ngram == 0 the launch IS kw_beam_logprobs's: cand_val / cand_idx are bitwise its results.
+ * With a workspace (each row over several workgroups) it is two launches on the stream: a slice cannot penalise a
+ * log-prob before the row's normaliser is known, so one workgroup per row first leaves (max, log sum exp) in two spare
+ * floats of the row's workspace record, and the split launch reads them -- kernel order, no in-launch hand-off. */
+int kw_beam_logprobs_rep(const kw_beam_logprobs_args* args, float penalty, int32_t ngram, kw_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -111,7 +111,52 @@ __device__ __forceinline__ uint64_t wave_best_key(uint64_t k) {
          (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)k, w);
 }
 
-__global__ __launch_bounds__(ST) void beam_logprobs_kernel(kw_beam_logprobs_args a) {
+// ---- repetition_penalty / no_repeat_ngram_size on the log-probs (kw_beam_logprobs_rep; the REP instantiations).
+// RepetitionPenaltyLogitsProcessor then NoRepeatNGramLogitsProcessor (TF/generation/logits_process.py:406-413,
+// 1121-1139) lead the processor list (TF/generation/utils.py:1174-1183) and see log_softmax(logits) in beam search
+// (:3380-3381), with no renormalisation after them.  Each workgroup turns its row's history ids[0 .. L) into two
+// vocabulary bitsets in LDS -- "occurs in the history" and "banned by an n-gram" -- and every log-prob the kernel
+// forms goes through rep_apply before the Whisper processors and the timestamp mass rule see it.
+constexpr int REP_VMAX = 65536, REP_WORDS = REP_VMAX / 32;
+
+template <int NT>
+__device__ __forceinline__ void rep_bitsets(uint32_t* hist, uint32_t* ban, const int64_t* __restrict__ ids, int L, int V,
+                                            float penalty, int ngram) {
+  const int tid = threadIdx.x;
+  const int nw = (V + 31) >> 5;
+  for (int i = tid; i < nw; i += NT) {
+    hist[i] = 0;
+    ban[i] = 0;
+  }
+  __syncthreads();
+  if (penalty != 1.0f) {
+    for (int p = tid; p < L; p += NT) {
+      const int64_t t = ids[p];
+      if (t >= 0 && t < V) atomicOr(&hist[t >> 5], 1u << (t & 31));
+    }
+  }
+  if (ngram > 0 && L >= ngram) {
+    const int64_t* tail = ids + (L - (ngram - 1));  // the history's last n-1 tokens
+    for (int i = tid; i + ngram <= L; i += NT) {
+      bool same = true;
+      for (int j = 0; j < ngram - 1 && same; ++j) same = ids[i + j] == tail[j];
+      if (!same) continue;
+      const int64_t t = ids[i + ngram - 1];
+      if (t >= 0 && t < V) atomicOr(&ban[t >> 5], 1u << (t & 31));
+    }
+  }
+  __syncthreads();
+}
+// (f32, a true division, from the element's own log-prob; a banned token ends as -inf whatever the penalty gave)
+__device__ __forceinline__ float rep_apply(const uint32_t* hist, const uint32_t* ban, float penalty, int v, float y) {
+  if ((hist[v >> 5] >> (v & 31)) & 1u) y = y < 0.f ? y * penalty : y / penalty;
+  if ((ban[v >> 5] >> (v & 31)) & 1u) y = -INFINITY;
+  return y;
+}
+
+template <bool REP>
+__device__ __forceinline__ void beam_logprobs_body(const kw_beam_logprobs_args& a, float penalty, int ngram) {
+  __shared__ uint32_t rep_hist[REP ? REP_WORDS : 1], rep_ban[REP ? REP_WORDS : 1];
   __shared__ float shf[ST / 64];
   __shared__ int shi[ST / 64][2];
   __shared__ RowState st_sh;
@@ -134,7 +179,12 @@ __global__ __launch_bounds__(ST) void beam_logprobs_kernel(kw_beam_logprobs_args
   for (int v = tid; v < V; v += ST) s += expf(x[v] - m);
   s = block_reduce_sum(s, shf);
   const float ls = logf(s);
-  auto lp = [&](int v) { return (x[v] - m) - ls; };
+  if constexpr (REP) rep_bitsets<ST>(rep_hist, rep_ban, ids, L, V, penalty, ngram);
+  auto lp = [&](int v) {
+    const float y = (x[v] - m) - ls;
+    if constexpr (REP) return rep_apply(rep_hist, rep_ban, penalty, v, y);
+    return y;
+  };
 
   int fin = 0;
   RowState st = row_state(ids, L, a.begin_index, a.ts_begin, a.no_ts_id, a.eos_id, a.return_timestamps,
@@ -191,6 +241,14 @@ __global__ __launch_bounds__(ST) void beam_logprobs_kernel(kw_beam_logprobs_args
   }
 }
 
+// (the kernels keep one symbol each: REP is a flag of the shared body, the plain launch's code is as it was)
+__global__ __launch_bounds__(ST) void beam_logprobs_kernel(kw_beam_logprobs_args a) {
+  beam_logprobs_body<false>(a, 1.0f, 0);
+}
+__global__ __launch_bounds__(ST) void beam_lp_rep_kernel(kw_beam_logprobs_args a, float penalty, int ngram) {
+  beam_logprobs_body<true>(a, penalty, ngram);
+}
+
 // ---- split-row variant: a row over BSPLIT workgroups (the one-workgroup kernel above walks a whole
 // vocabulary row serially in several passes; at R = 160-320 running rows that is most of a step).
 // Each slice keeps its logits in registers and publishes: the raw maximum and sum of exp (the
@@ -200,6 +258,8 @@ __global__ __launch_bounds__(ST) void beam_logprobs_kernel(kw_beam_logprobs_args
 // last arriver merges the normaliser, applies the timestamp rule, turns candidates into log-probs
 // lp = (x - m) - log(s) and keeps the k best by (lp desc, token asc).
 constexpr int BSPLIT = 8, BT_S = 512, BUNR = 16, KP = KMAX + 4, BPART = 96;
+constexpr int REP_NORM = BPART - 2;  // REP: the row's (max, log sum exp) in its first slice record
+static_assert(9 + 4 * KP <= REP_NORM, "the slice record's published floats must leave the normaliser's two alone");
 
 __device__ __forceinline__ void bl_argmax(float& best, int& bi, int& bt, float* shf, int* shi) {
 #pragma unroll
@@ -238,7 +298,16 @@ __device__ __forceinline__ float bl_sum(float v, float* sh) {
   return r;
 }
 
-__global__ __launch_bounds__(BT_S) void beam_logprobs_split_kernel(kw_beam_logprobs_args a) {
+// REP: the processors act on log-probs and are not shift invariant, so a slice cannot stay in raw-logit space until
+// the merge.  A launch of its own ahead of this one (beam_rep_norm_kernel, one workgroup per row) leaves the row's
+// normaliser -- max and log(sum exp), the one-workgroup kernel's arithmetic -- in two spare floats of the row's first
+// slice record (a record publishes at most 9 + 4 KP of its BPART floats, and the merge reads no more); every slice
+// turns its logits into penalised / banned log-probs up front, and the merge takes the candidates' values as they
+// are instead of normalising them.  (Each slice taking the normaliser itself, eight reads of every row, cost 77 us at
+// R = 160, V = 51866 -- more than the whole plain launch.)
+template <bool REP>
+__device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_args& a, float penalty, int ngram) {
+  __shared__ uint32_t rep_hist[REP ? REP_WORDS : 1], rep_ban[REP ? REP_WORDS : 1];
   __shared__ RowState st_sh;
   __shared__ float pub[BPART];
   if (*a.done) return;
@@ -260,6 +329,16 @@ __global__ __launch_bounds__(BT_S) void beam_logprobs_split_kernel(kw_beam_logpr
     const uint8_t mr = a.suppress_mask[vc];
     xv[u] = v < v1 ? xr : -INFINITY;
     mk[u] = v < v1 ? mr != 0 : true;
+  }
+  if constexpr (REP) {
+    const float* nrm = reinterpret_cast<const float*>(a.workspace) + (int64_t)r * BSPLIT * BPART + REP_NORM;
+    const float m = nrm[0], ls = nrm[1];  // (beam_rep_norm_kernel, the launch before this one)
+    rep_bitsets<BT_S>(rep_hist, rep_ban, ids, L, V, penalty, ngram);
+#pragma unroll
+    for (int u = 0; u < BUNR; ++u) {
+      const int v = v0 + tid + u * BT_S;
+      if (v < v1) xv[u] = rep_apply(rep_hist, rep_ban, penalty, v, (xv[u] - m) - ls);
+    }
   }
   // row state from the history (as kwp::row_state, BT_S threads): the last timestamp position travels with
   // its token in one 64-bit key (no dependent reload), the last two tokens are read up front
@@ -497,7 +576,8 @@ __global__ __launch_bounds__(BT_S) void beam_logprobs_split_kernel(kw_beam_logpr
       const float sval = ld(q, base + 2 * j);
       const int idx = __float_as_int(ld(q, base + 2 * j + 1));
       if (idx != 0x7fffffff) {
-        c[t] = sval > -INFINITY ? (sval - m) - ls : -INFINITY;
+        if constexpr (REP) c[t] = sval;  // (a log-prob already, not renormalised)
+        else c[t] = sval > -INFINITY ? (sval - m) - ls : -INFINITY;
         ci3[t] = idx;
       }
     }
@@ -536,6 +616,33 @@ __global__ __launch_bounds__(BT_S) void beam_logprobs_split_kernel(kw_beam_logpr
         a.cand_idx[(int64_t)r * K + j] = ci3[t];
         kk[t] = 0;
       }
+  }
+}
+
+__global__ __launch_bounds__(BT_S) void beam_logprobs_split_kernel(kw_beam_logprobs_args a) {
+  beam_logprobs_split_body<false>(a, 1.0f, 0);
+}
+__global__ __launch_bounds__(BT_S) void beam_lp_rep_split_kernel(kw_beam_logprobs_args a, float penalty, int ngram) {
+  beam_logprobs_split_body<true>(a, penalty, ngram);
+}
+// the row's log_softmax normaliser, as beam_logprobs_body takes it, for the launch above
+__global__ __launch_bounds__(ST) void beam_rep_norm_kernel(kw_beam_logprobs_args a) {
+  __shared__ float shf[ST / 64];
+  if (*a.done) return;
+  const int r = blockIdx.x, tid = threadIdx.x, V = (int)a.V;
+  const float* x = a.logits + (int64_t)r * a.V;
+  float m = -INFINITY;
+#pragma unroll 8
+  for (int v = tid; v < V; v += ST) m = fmaxf(m, x[v]);
+  m = block_reduce_max(m, shf);
+  float s = 0.f;
+#pragma unroll 8
+  for (int v = tid; v < V; v += ST) s += expf(x[v] - m);
+  s = block_reduce_sum(s, shf);
+  if (tid == 0) {
+    float* nrm = reinterpret_cast<float*>(a.workspace) + (int64_t)r * BSPLIT * BPART + REP_NORM;
+    nrm[0] = m;
+    nrm[1] = logf(s);
   }
 }
 
@@ -790,6 +897,26 @@ extern "C" int kw_beam_logprobs(const kw_beam_logprobs_args* a, kw_stream_t stre
     hipLaunchKernelGGL(beam_logprobs_split_kernel, dim3((unsigned)a->R, BSPLIT), dim3(BT_S), 0, (hipStream_t)stream, *a);
   else
     hipLaunchKernelGGL(beam_logprobs_kernel, dim3((unsigned)a->R), dim3(ST), 0, (hipStream_t)stream, *a);
+  KW_CHECK_LAUNCH();
+  return KW_OK;
+}
+
+extern "C" int kw_beam_logprobs_rep(const kw_beam_logprobs_args* a, float penalty, int32_t ngram, kw_stream_t stream) {
+  if (!a || !a->logits || !a->suppress_mask || !a->ids || !a->cur_len || !a->cand_val || !a->cand_idx || !a->done ||
+      a->R <= 0 || a->V <= 0 || a->k < 1 || a->k > KMAX || (a->n_begin_suppress > 0 && !a->begin_suppress) ||
+      !(penalty > 0.f) || !isfinite(penalty) || ngram < 0)
+    return kw_set_error_msg(KW_EINVAL,
+                            "kw_beam_logprobs_rep: invalid arguments (k <= 16, penalty > 0 and finite, ngram >= 0)");
+  if (a->V > REP_VMAX) return kw_set_error_msg(KW_EUNSUPPORTED, "kw_beam_logprobs_rep: V > 65536");
+  if (penalty == 1.0f && ngram == 0) return kw_beam_logprobs(a, stream);  // both off: that very launch
+  if (a->workspace && a->ws_bytes >= kw_beam_logprobs_workspace(a->R) && a->V <= (int64_t)BSPLIT * BT_S * BUNR) {
+    hipLaunchKernelGGL(beam_rep_norm_kernel, dim3((unsigned)a->R), dim3(ST), 0, (hipStream_t)stream, *a);
+    hipLaunchKernelGGL(beam_lp_rep_split_kernel, dim3((unsigned)a->R, BSPLIT), dim3(BT_S), 0, (hipStream_t)stream, *a,
+                       penalty, (int)ngram);
+  } else {
+    hipLaunchKernelGGL(beam_lp_rep_kernel, dim3((unsigned)a->R), dim3(ST), 0, (hipStream_t)stream, *a, penalty,
+                       (int)ngram);
+  }
   KW_CHECK_LAUNCH();
   return KW_OK;
 }

@@ -497,13 +497,14 @@ void dec_lm_greedy(const Tensor& x, const Tensor& W, const optional<Tensor>& bia
 
 // ---- beam search step ---------------------------------------------------------------------------------
 // cfg = [return_timestamps, ts_begin, no_ts_id, eos_id, max_initial_ts, begin_index, k]
-void beam_logprobs(const Tensor& logits, const Tensor& suppress_mask, const optional<Tensor>& begin_suppress,
-                   const Tensor& ids, const Tensor& cur_len, Tensor& cand_val, Tensor& cand_idx, const Tensor& done,
-                   optional<Tensor> workspace, std::vector<int64_t> cfg) {
-  const char* w = "kw_beam_logprobs";
+// (penalty / ngram: kw_beam_logprobs_rep when rep, else kw_beam_logprobs)
+void beam_logprobs_impl(const char* w, bool rep, const Tensor& logits, const Tensor& suppress_mask,
+                        const optional<Tensor>& begin_suppress, const Tensor& ids, const Tensor& cur_len, Tensor& cand_val,
+                        Tensor& cand_idx, const Tensor& done, optional<Tensor> workspace, std::vector<int64_t> cfg,
+                        double penalty, int64_t ngram) {
   dev(logits, w), dev(suppress_mask, w), dev(begin_suppress, w), dev(ids, w), dev(cur_len, w);
   dev(cand_val, w), dev(cand_idx, w), dev(done, w), dev(workspace, w);
-  TORCH_CHECK_VALUE(cfg.size() == 7, "kw_beam_logprobs: cfg must hold 7 integers");
+  TORCH_CHECK_VALUE(cfg.size() == 7, w, ": cfg must hold 7 integers");
   kw_beam_logprobs_args a{};
   a.logits = ptr<const float>(logits);
   a.R = logits.size(0), a.V = logits.size(1);
@@ -524,7 +525,44 @@ void beam_logprobs(const Tensor& logits, const Tensor& suppress_mask, const opti
   a.workspace = optr<void>(workspace);
   a.ws_bytes = workspace.has_value() ? (size_t)workspace->numel() * workspace->element_size() : 0;
   c10::DeviceGuard g(logits.device());
-  check(kw_beam_logprobs(&a, stream_of(logits)), w);
+  if (rep) {
+    TORCH_CHECK_VALUE(ngram >= INT32_MIN && ngram <= INT32_MAX, w, ": ngram out of range");
+    check(kw_beam_logprobs_rep(&a, (float)penalty, (int32_t)ngram, stream_of(logits)), w);
+  } else {
+    check(kw_beam_logprobs(&a, stream_of(logits)), w);
+  }
+}
+
+void beam_logprobs(const Tensor& logits, const Tensor& suppress_mask, const optional<Tensor>& begin_suppress,
+                   const Tensor& ids, const Tensor& cur_len, Tensor& cand_val, Tensor& cand_idx, const Tensor& done,
+                   optional<Tensor> workspace, std::vector<int64_t> cfg) {
+  beam_logprobs_impl("kw_beam_logprobs", false, logits, suppress_mask, begin_suppress, ids, cur_len, cand_val, cand_idx,
+                     done, workspace, cfg, 1.0, 0);
+}
+
+// kw_beam_logprobs with repetition_penalty / no_repeat_ngram_size on the log-probs (cfg as beam_logprobs)
+void beam_logprobs_rep(const Tensor& logits, const Tensor& suppress_mask, const optional<Tensor>& begin_suppress,
+                       const Tensor& ids, const Tensor& cur_len, Tensor& cand_val, Tensor& cand_idx, const Tensor& done,
+                       optional<Tensor> workspace, std::vector<int64_t> cfg, double penalty, int64_t ngram) {
+  beam_logprobs_impl("kw_beam_logprobs_rep", true, logits, suppress_mask, begin_suppress, ids, cur_len, cand_val,
+                     cand_idx, done, workspace, cfg, penalty, ngram);
+}
+
+// ---- repetition_penalty / no_repeat_ngram_size in place on f32 scores [R][V] ------------------------------
+void repeat_process(Tensor& scores, const Tensor& ids, const Tensor& cur_len, double penalty, int64_t ngram) {
+  const char* w = "kw_repeat_process";
+  dev(scores, w), dev(ids, w), dev(cur_len, w);
+  TORCH_CHECK_VALUE(scores.dim() == 2 && scores.is_contiguous() && scores.scalar_type() == at::kFloat,
+                    "kw_repeat_process: scores must be a contiguous (R, V) float32 tensor");
+  TORCH_CHECK_VALUE(ids.dim() == 2 && ids.scalar_type() == at::kLong && ids.stride(1) == 1 &&
+                        ids.size(0) >= scores.size(0) && cur_len.scalar_type() == at::kInt && cur_len.numel() >= 1,
+                    "kw_repeat_process: ids int64 [R][ids_stride], cur_len int32 [1]");
+  TORCH_CHECK_VALUE(ngram >= INT32_MIN && ngram <= INT32_MAX, "kw_repeat_process: ngram out of range");
+  c10::DeviceGuard g(scores.device());
+  // (the kernel reads ids[r][0 .. min(*cur_len, row length)): the row length, not the stride, bounds the history)
+  check(kw_repeat_process(ptr<float>(scores), scores.size(0), scores.size(1), ptr<const int64_t>(ids), ids.stride(0),
+                          ptr<const int32_t>(cur_len), (float)penalty, (int32_t)ngram, stream_of(scores)),
+        w);
 }
 
 // cfg = [B, num_beams, V, begin_index, max_length, eos_id, fill_id, early_stopping]
@@ -699,6 +737,10 @@ TORCH_LIBRARY(kw, m) {
         "Tensor(f!) workspace, int[] lm_geo, float ln_eps, int[] cfg) -> ()");
   m.def("beam_logprobs(Tensor logits, Tensor suppress_mask, Tensor? begin_suppress, Tensor ids, Tensor cur_len, "
         "Tensor(a!) cand_val, Tensor(b!) cand_idx, Tensor done, Tensor(c!)? workspace, int[] cfg) -> ()");
+  m.def("beam_logprobs_rep(Tensor logits, Tensor suppress_mask, Tensor? begin_suppress, Tensor ids, Tensor cur_len, "
+        "Tensor(a!) cand_val, Tensor(b!) cand_idx, Tensor done, Tensor(c!)? workspace, int[] cfg, float penalty, "
+        "int ngram) -> ()");
+  m.def("repeat_process(Tensor(a!) scores, Tensor ids, Tensor cur_len, float penalty, int ngram) -> ()");
   m.def("beam_select(Tensor cand_val, Tensor cand_idx, Tensor(a!) ids, Tensor(b!)? bp, Tensor(c!) run_scores, "
         "Tensor(d!) fin_seq, Tensor(e!) fin_score, Tensor(f!) fin_len, Tensor(g!) fin_flag, Tensor(h!) unsat, "
         "Tensor(i!) cur_len, Tensor(j!) counter, Tensor(k!) go, Tensor(l!) done, Tensor(m!) item_flags, int[] cfg, "
@@ -731,6 +773,8 @@ TORCH_LIBRARY_IMPL(kw, CUDA, m) {
   m.impl("sample_step", &sample_step);
   m.impl("dec_lm_greedy", &dec_lm_greedy);
   m.impl("beam_logprobs", &beam_logprobs);
+  m.impl("beam_logprobs_rep", &beam_logprobs_rep);
+  m.impl("repeat_process", &repeat_process);
   m.impl("beam_select", &beam_select);
   m.impl("align_capture", &align_capture);
   m.impl("align_weights", &align_weights);

@@ -139,6 +139,10 @@ class GenerationConstants:
     # [layer, head] pairs of the cross-attention heads token timestamps are read from (return_token_timestamps);
     # None = the generation config has none (HF: the attribute is missing)
     alignment_heads: list | None = None
+    # GenerationMixin's anti-repetition processors (None = off, as 1.0 / 0): generate() reads them when the call does
+    # not pass the keyword
+    repetition_penalty: float | None = None
+    no_repeat_ngram_size: int | None = None
 
     @property
     def timestamp_begin(self) -> int:

@@ -499,7 +499,7 @@ class DecodeSession:
 
     def generate(self, prompt: torch.Tensor, gen, *, max_length: int, return_timestamps: bool,
                  check_every: int = 4, use_graph: bool = True, record_scores: bool = False, align=None,
-                 num_frames=None, median_filter_width: int = 7, sample=None, key_start=None):
+                 num_frames=None, median_filter_width: int = 7, sample=None, key_start=None, repeat=None):
         """Greedy loop of GenerationMixin._sample (TF/generation/utils.py:2783-2941).
 
         ``sample``: None (the greedy path, unchanged), or a dict -- ``temperature`` (0 = argmax), ``seed``, ``attempt``
@@ -522,7 +522,14 @@ class DecodeSession:
         ``key_start``: per row, the number of leading pad positions of a left-padded ``prompt`` (the
         decoder_attention_mask of a conditioned pass, TF generation_whisper.py:1908): the row attends keys from there
         on, positions stay the plain arange.  None or all zero: exactly the unmasked plans and graphs.  Otherwise the
-        self-attention runs kw_self_attn_step_masked in the prefill and in every step (never the fused self block)."""
+        self-attention runs kw_self_attn_step_masked in the prefill and in every step (never the fused self block).
+
+        ``repeat``: (repetition_penalty, no_repeat_ngram_size), or None.  None or (1.0, 0): exactly today's plans, graph
+        keys and launches.  Otherwise kw_repeat_process runs on the raw logits between the LM head and the greedy /
+        sampled step -- in the prefill too (the first token is penalised against the prompt) and in every step, on the
+        same stream -- so the step's tail is never the fused LM-head + greedy launch.  With ``record_scores`` the
+        logits recorded per step are the penalised ones; ``self.raw_logits`` keeps the LM head's own."""
+        repeat = _norm_repeat(repeat)
         masked = self._set_key_start(key_start)
         self._keep_prefill(prompt.shape[1])
         if masked and align is not None:
@@ -578,6 +585,8 @@ class DecodeSession:
             key += ("sample",)
         if masked:
             key += ("masked",)
+        if repeat is not None:
+            key += (("repeat",) + repeat,)
         cfg = self._greedy_cfg.get(key)
         if cfg is None:
             sup = torch.zeros((self.eng.shape.vocab_size,), dtype=torch.uint8)
@@ -600,16 +609,35 @@ class DecodeSession:
                                           self.unfinished, self.counter, self.n_unfinished, scores_out=score_buf,
                                           workspace=self.samp_ws, **pcfg)
             cfg = dict(sampler=sampler, score_buf=score_buf, graph=None, P=P)
+            if repeat is not None:
+                cfg["repeat"] = ops.RepeatPlan(self.logits, self.ids, self.cur_len, penalty=repeat[0], ngram=repeat[1])
             if len(self._greedy_cfg) >= 8:  # bound the cache (each entry may hold a graph)
                 self._greedy_cfg.pop(next(iter(self._greedy_cfg)))
             self._greedy_cfg[key] = cfg
         sampler, score_buf = cfg["sampler"], cfg["score_buf"]
         self.scores = [] if record_scores else None
+        self.raw_logits = [] if record_scores and repeat is not None else None
+        rep_plan = cfg.get("repeat")
+
+        def processed_tail(tail):
+            """The step's token choice, behind the repetition processors where the call has them."""
+            if rep_plan is None:
+                return tail
+
+            def run():
+                if self.raw_logits is not None:
+                    self.raw_logits.append(self.logits.clone())
+                rep_plan()
+                tail()
+            return run
+
         # prefill (replayed from a graph cached with the configuration: ~260 launches otherwise go
         # through Python one by one)
+        first_tail = processed_tail(sampler)
+
         def prefill():
             self._run_prefill(P, self.eng.prefill_streams, masked)
-            sampler()
+            first_tail()
 
         pg = cfg.get("prefill_graph")
         if pg is None and use_graph and not record_scores:
@@ -631,7 +659,7 @@ class DecodeSession:
         tail = sampler
         s = self.eng.shape
         if (self.eng.packed and self.nb == 1 and self.eng.fuse_lm_greedy and not return_timestamps and not record_scores
-                and sample is None and ops.lm_greedy_supported(B, s.vocab_size, s.d_model)):
+                and sample is None and rep_plan is None and ops.lm_greedy_supported(B, s.vocab_size, s.d_model)):
             tail = cfg.get("lm_greedy")
             if tail is None:
                 if self._lmg_ws is None:
@@ -647,6 +675,7 @@ class DecodeSession:
             assert getattr(step_seq[-1], "tag", None) == "lm_head"
             step_seq = step_seq[:-1]
         self.lm_greedy_last = tail is not sampler
+        tail = processed_tail(tail)
 
         def one_step():
             self._run(step_seq)
@@ -765,11 +794,17 @@ class DecodeSession:
 
 
     def generate_beam(self, prompt: torch.Tensor, gen, *, num_beams: int, max_length: int, return_timestamps: bool,
-                      length_penalty: float = 1.0, early_stopping=False, check_every: int = 4, use_graph: bool = True):
+                      length_penalty: float = 1.0, early_stopping=False, check_every: int = 4, use_graph: bool = True,
+                      repeat=None):
         """``GenerationMixin._beam_search`` (TF/generation/utils.py:3208-3527) on device, num_return_sequences 1.
 
         ``prompt`` (B, P) per item.  Returns host int64 (B, P + generated) -- the best finished beam of each
-        item, pad-filled, cropped to the batch's longest -- as the reference returns ``sequences``."""
+        item, pad-filled, cropped to the batch's longest -- as the reference returns ``sequences``.
+
+        ``repeat``: (repetition_penalty, no_repeat_ngram_size), or None.  None or (1.0, 0): exactly today's plan and
+        graphs.  Otherwise kw_beam_logprobs_rep takes kw_beam_logprobs' place: both processors act on every row's
+        log-probs, from the row's own re-ordered history, before the Whisper processors."""
+        repeat = _norm_repeat(repeat)
         B, nb, R = self.B, self.nb, self.R
         if nb != num_beams or nb < 2:
             raise ValueError("session beam width mismatch")
@@ -788,6 +823,8 @@ class DecodeSession:
         key = ("beam", max_length, P, bool(return_timestamps), float(length_penalty), str(early_stopping), fill,
                tuple(gen.suppress_tokens or ()), tuple(gen.begin_suppress_tokens or ()), gen.timestamp_begin,
                gen.no_timestamps_token_id, gen.eos_token_id, gen.max_initial_timestamp_index)
+        if repeat is not None:
+            key += (("repeat",) + repeat,)
         cfg = self._greedy_cfg.get(key)
         if cfg is None:
             st = dict(
@@ -816,7 +853,7 @@ class DecodeSession:
                                     no_ts_id=gen.no_timestamps_token_id, eos_id=gen.eos_token_id,
                                     max_initial_ts=gen.max_initial_timestamp_index, begin_index=P,
                                     max_length=max_length, fill_id=fill, length_penalty=length_penalty,
-                                    early_stopping=early_stopping)
+                                    early_stopping=early_stopping, repeat=repeat)
             cfg = dict(st=st, step=step, graph=None, prefill_graph=None, P=P)
             if len(self._greedy_cfg) >= 8:
                 self._greedy_cfg.pop(next(iter(self._greedy_cfg)))
@@ -872,6 +909,14 @@ class DecodeSession:
         fin_len = st["fin_len"][:, 0].cpu().numpy()
         out = st["fin_seq"][:, 0].cpu().numpy()
         return out[:, : P + int(fin_len.max())]
+
+
+def _norm_repeat(repeat):
+    """``repeat`` as (penalty, ngram) with the values checked, or None when both processors are off."""
+    if repeat is None:
+        return None
+    penalty, ngram = ops.check_repeat(*repeat)
+    return None if (penalty == 1.0 and ngram == 0) else (penalty, ngram)
 
 
 def _reference_length(ids: np.ndarray, P: int, eos: int, max_length: int) -> np.ndarray:

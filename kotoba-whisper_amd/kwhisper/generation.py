@@ -24,6 +24,13 @@ TF/models/whisper/generation_whisper.py:383-968):
     ``_prepare_decoder_input_ids`` -- the previous text behind ``<|startofprev|>``, left-padded to the pass's longest
     row -- built on the host (``build_pass_input``); the pads are masked in the decoder self-attention by a per-row
     first key (kw_self_attn_step_masked), positions stay the plain arange     :1853-1918, :126-235, :1119-1126, :905-915
+  * ``repetition_penalty`` / ``no_repeat_ngram_size`` (from the call, else the generation config):
+    RepetitionPenaltyLogitsProcessor -> NoRepeatNGramLogitsProcessor ahead of the Whisper processors, on device in
+    every step of every pass and every fallback attempt -- on the raw logits for the greedy and sampled tails
+    (kw_repeat_process, csrc/repeat.hip), on the log-probs for beams (kw_beam_logprobs_rep, csrc/beam.hip)
+                                              TF/generation/utils.py:1174-1183, TF/generation/logits_process.py:406-413, 1121-1139
+    ``generate_multitask``, ``pseudo_label*`` and ``ASRPipeline(generate_kwargs=...)`` forward their keywords to
+    ``generate`` unchanged, so the two reach it from there as well.
 
 Deliberate differences of the fallback from transformers 5.15.0:
   * ``no_speech_threshold`` without ``logprob_threshold`` raises ``ValueError`` (the reference dies on an unbound local);
@@ -62,6 +69,7 @@ _SUPPORTED = {
     "output_scores", "output_logits", "time_precision", "time_precision_features", "num_segment_frames",
     "synced_gpus", "force_unique_generate_call", "prefix_allowed_tokens_fn", "prompt_condition_type",
     "monitor_progress", "use_cache", "num_return_sequences", "length_penalty", "early_stopping",
+    "repetition_penalty", "no_repeat_ngram_size",
 }
 
 
@@ -223,6 +231,7 @@ class KWhisperForConditionalGeneration:
         if isinstance(gen, dict):
             gen = GenerationConstants(**gen)
         num_beams = kwargs.get("num_beams", gen.num_beams or 1)
+        repeat = _repeat_arguments(kwargs, gen)
         # decoding fallback: the thresholds from the call or the generation config (_set_thresholds_and_condition,
         # generation_whisper.py:1703-1729) and the temperature schedule (:735); `do_sample` itself is overridden by
         # the schedule (:1002-1010)
@@ -437,13 +446,14 @@ class KWhisperForConditionalGeneration:
             sess = self._session(cur, num_beams)
             sess.set_encoder_output(enc, key=enc_key)
             skip = [False] * cur
+            rep_kw = {} if repeat is None else {"repeat": repeat}  # (None: the session calls as they ever were)
             if fallback:
                 sot = None
                 if passes == 0 and feats is not None and whole and self._sot_logits is not None \
                         and self._sot_logits.shape[0] == cur:
                     sot = self._sot_logits  # language detection ran this very position on these features
                 ids, skip, attempts = self._generate_with_fallback(sess, prompt, gen, eff_max, return_timestamps,
-                                                                   temperatures, thr, batch_map, sot, key_start)
+                                                                   temperatures, thr, batch_map, sot, key_start, repeat)
                 fallback_log.append(attempts)
                 for rec in attempts:  # (:1088-1093): a row accepted at a temperature of 0.5 or more loses its conditioning
                     for p in rec["rows"]:
@@ -451,20 +461,20 @@ class KWhisperForConditionalGeneration:
             elif num_beams > 1:
                 ids = sess.generate_beam(torch.from_numpy(prompt), gen, num_beams=num_beams, max_length=eff_max,
                                          return_timestamps=return_timestamps, length_penalty=length_penalty,
-                                         early_stopping=early_stopping)
+                                         early_stopping=early_stopping, **rep_kw)
             elif token_ts:
                 # per pass: num_frames - seek of the rows still running (generation_whisper.py:1146-1150)
                 nf = None if ts_frames is None else [int(ts_frames[p] - seek[p]) for p in batch_map]
                 sess.keep_alignment = self.record_alignment
                 ids = sess.generate(torch.from_numpy(prompt), gen, max_length=eff_max,
                                     return_timestamps=return_timestamps, align=align, num_frames=nf,
-                                    median_filter_width=s.median_filter_width)
+                                    median_filter_width=s.median_filter_width, **rep_kw)
                 pass_ts = _pass_token_timestamps(sess.align_out["frames"], P, ids.shape[1])
                 if self.record_alignment:
                     align_log.append(dict(sess.align_out, rows=[int(p) for p in batch_map], num_input_ids=P))
             else:
                 ids = sess.generate(torch.from_numpy(prompt), gen, max_length=eff_max,
-                                    return_timestamps=return_timestamps, key_start=key_start)
+                                    return_timestamps=return_timestamps, key_start=key_start, **rep_kw)
             passes += 1
             last_ids = ids
             pass_log.append(([int(p) for p in batch_map], [int(seek[p]) for p in batch_map],
@@ -518,12 +528,13 @@ class KWhisperForConditionalGeneration:
         return res
 
     def _generate_with_fallback(self, sess, prompt, gen, max_length, return_timestamps, temperatures, thr, batch_map,
-                                sot_logits=None, key_start=None):
+                                sot_logits=None, key_start=None, repeat=None):
         """One seek pass's attempt loop (``generate_with_fallback``, generation_whisper.py:1001-1116): decode at each
         temperature of the schedule in turn -- 0 greedy, above 0 sampled -- re-decoding only the rows whose
         ``_need_fallback`` decision asks for it, in the same session (its cross K/V stays; no re-encode); the last
         temperature's result is accepted.  Returns the pass's ids (cur, L) with every row from the attempt that was
-        accepted for it (right-padded), the rows to skip, and the per-attempt record kept in ``stats["fallback"]``."""
+        accepted for it (right-padded), the rows to skip, and the per-attempt record kept in ``stats["fallback"]``.
+        ``repeat`` goes to every attempt (the reference copies the generation config per attempt)."""
         cur, P = prompt.shape
         pad, eos, V = gen.pad_token_id, gen.eos_token_id, self.engine.shape.vocab_size
         nsp = None
@@ -540,6 +551,7 @@ class KWhisperForConditionalGeneration:
             active[rows] = True
             ids = sess.generate(torch.from_numpy(prompt), gen, max_length=max_length, return_timestamps=return_timestamps,
                                 **({} if key_start is None else {"key_start": key_start}),
+                                **({} if repeat is None else {"repeat": repeat}),
                                 sample=dict(temperature=t, seed=self._seed, active=active,
                                             attempt=(self._lane << 24) | (self._attempts & 0xFFFFFF)))
             rec = dict(rows=[int(batch_map[i]) for i in rows], temperature=float(t), avg_logprob=[], compression_ratio=[],
@@ -650,6 +662,32 @@ class KWhisperForConditionalGeneration:
                 r.pop()
         arr = np.asarray(rows, dtype=np.int64)
         return np.broadcast_to(arr, (B, arr.shape[1])).copy()
+
+
+def _repeat_arguments(kwargs, gen):
+    """``repetition_penalty`` / ``no_repeat_ngram_size`` from the call, else the generation config, as the ``repeat``
+    pair of ``DecodeSession.generate`` -- None when neither processor would be built (TF generation/utils.py:1174-1183:
+    a penalty of None or 1.0, an n-gram size of None or 0)."""
+    penalty = kwargs.get("repetition_penalty")
+    if penalty is None:
+        penalty = getattr(gen, "repetition_penalty", None)
+    ngram = kwargs.get("no_repeat_ngram_size")
+    if ngram is None:
+        ngram = getattr(gen, "no_repeat_ngram_size", None)
+    if penalty is not None and penalty != 1.0:
+        # RepetitionPenaltyLogitsProcessor.__init__ (TF generation/logits_process.py:390-392)
+        if not isinstance(penalty, float) or not (penalty > 0):
+            raise ValueError(f"`penalty` has to be a strictly positive float, but is {penalty}")
+    else:
+        penalty = 1.0
+    # (utils.py:1182: the processor is built for a size that is not None and > 0; its own check wants an int)
+    if ngram is not None and ngram > 0:
+        if not isinstance(ngram, int):
+            raise ValueError(f"`ngram_size` has to be a strictly positive integer, but is {ngram}")
+        ngram = int(ngram)
+    else:
+        ngram = 0
+    return None if (penalty == 1.0 and ngram == 0) else (penalty, ngram)
 
 
 def build_pass_input(init_tokens, segments, batch_map, do_condition, prompt_ids, gen, max_target_positions,

@@ -5,7 +5,7 @@ ops wrap the ABI"), which fills the C ABI's argument block and launches on torch
 the kernels are ordinary torch ops to the dispatcher, to ``torch.cuda.graph`` capture and to
 ``torch.compile`` (fake implementations are registered: every op mutates its outputs and returns nothing).
 Tensors are plumbing only (device memory + stream); all arithmetic happens in the HIP kernels of
-``libkwhisper.so``.  The plan classes (``GemmPlan``, ``DecLinearPlan``, ``SamplerPlan``, ``SamplePlan``, ``BeamStepPlan``)
+``libkwhisper.so``.  The plan classes (``GemmPlan``, ``DecLinearPlan``, ``SamplerPlan``, ``SamplePlan``, ``RepeatPlan``, ``BeamStepPlan``)
 validate once and keep the op arguments, so decode steps replay without re-validation.
 
 ``set_backend("ctypes")`` routes the same calls through the ctypes binding of the C ABI instead (used by
@@ -759,12 +759,49 @@ class LmGreedyPlan:
             L.check(_lib().kw_dec_lm_greedy(self._ra, self._rg, _s()), "kw_dec_lm_greedy")
 
 
+def check_repeat(penalty, ngram):
+    """(penalty as the f32 the kernels take, ngram) of a ``repeat`` pair; ValueError as the entry points' KW_EINVAL."""
+    penalty, ngram = float(penalty), int(ngram)
+    if not (penalty > 0.0) or penalty == float("inf") or ngram < 0 or ngram > 0x7fffffff:
+        raise ValueError("repeat: penalty must be a finite float > 0 and ngram an int >= 0")
+    return penalty, ngram
+
+
+class RepeatPlan:
+    """Pre-built ``kw_repeat_process`` call: repetition_penalty (1.0 = off) and no_repeat_ngram_size (0 = off) in place
+    on the f32 ``scores`` [R][V], from every row's history ``ids[r][0 .. *cur_len)`` (the device scalar, so a captured
+    step replays).  Runs between the LM head and ``SamplerPlan`` / ``SamplePlan``."""
+
+    def __init__(self, scores, ids, cur_len, *, penalty, ngram):
+        _cuda(scores, ids, cur_len)
+        penalty, ngram = check_repeat(penalty, ngram)
+        if scores.dim() != 2 or scores.dtype != torch.float32 or not scores.is_contiguous():
+            raise ValueError("kw_repeat_process: scores must be a contiguous (R, V) float32 tensor")
+        if (ids.dim() != 2 or ids.dtype != torch.int64 or ids.stride(1) != 1 or ids.shape[0] < scores.shape[0]
+                or cur_len.dtype != torch.int32 or cur_len.numel() < 1):
+            raise ValueError("kw_repeat_process: ids int64 [R][ids_stride], cur_len int32 [1]")
+        self._keep = (scores, ids, cur_len)
+        self._targs = (scores, ids, cur_len, penalty, ngram)
+        R, V = scores.shape
+        self._cargs = (scores.data_ptr(), R, V, ids.data_ptr(), ids.stride(0), cur_len.data_ptr(), penalty, ngram)
+
+    def __call__(self):
+        if _BACKEND == "torch":
+            _kw().repeat_process(*self._targs)
+        else:
+            a = self._cargs
+            L.check(_lib().kw_repeat_process(ctypes.c_void_p(a[0]), a[1], a[2], ctypes.c_void_p(a[3]), a[4],
+                                             ctypes.c_void_p(a[5]), a[6], a[7], _s()), "kw_repeat_process")
+
+
 class BeamStepPlan:
-    """Pre-built ``kw_beam_logprobs`` + ``kw_beam_select`` calls for one beam-search step."""
+    """Pre-built ``kw_beam_logprobs`` + ``kw_beam_select`` calls for one beam-search step.  ``repeat`` = (penalty,
+    ngram): ``kw_beam_logprobs_rep`` takes ``kw_beam_logprobs``'s place (None: exactly the plain launch)."""
 
     def __init__(self, st, logits, suppress_mask, begin_suppress, *, return_timestamps, ts_begin, no_ts_id, eos_id,
-                 max_initial_ts, begin_index, max_length, fill_id, length_penalty, early_stopping):
+                 max_initial_ts, begin_index, max_length, fill_id, length_penalty, early_stopping, repeat=None):
         """``st``: a dict of the device state tensors (see DecodeSession.generate_beam)."""
+        self._rep = None if repeat is None else check_repeat(*repeat)
         self._keep = (st, logits, suppress_mask, begin_suppress)
         R, V = logits.shape
         B, nb = st["fin_score"].shape
@@ -813,10 +850,16 @@ class BeamStepPlan:
     def __call__(self):
         if _BACKEND == "torch":
             kw = _kw()
-            kw.beam_logprobs(*self._tlp)
+            if self._rep is None:
+                kw.beam_logprobs(*self._tlp)
+            else:
+                kw.beam_logprobs_rep(*self._tlp, *self._rep)
             kw.beam_select(*self._tsel)
         else:
-            L.check(_lib().kw_beam_logprobs(self._ra, _s()), "kw_beam_logprobs")
+            if self._rep is None:
+                L.check(_lib().kw_beam_logprobs(self._ra, _s()), "kw_beam_logprobs")
+            else:
+                L.check(_lib().kw_beam_logprobs_rep(self._ra, self._rep[0], self._rep[1], _s()), "kw_beam_logprobs_rep")
             L.check(_lib().kw_beam_select(self._rb, _s()), "kw_beam_select")
 
 
