@@ -555,6 +555,18 @@ typedef struct {
 
 int kw_beam_select(const kw_beam_select_args* args, kw_stream_t stream);
 
+/* kw_beam_select that also records who produced what (additive, ABI 112 unchanged; token timestamps under beam
+ * search need the reference's beam_indices).  Everything kw_beam_select writes is written bit for bit the same; two
+ * more outputs, both int32 on the device:
+ *   parent_log [max_length][B * num_beams]: the step at cur_len = L writes row L -- parent_log[L][r] is the running
+ *     row (of the whole batch, b * num_beams + beam) that next running row r continues;
+ *   fin_parent [B][num_beams]: for every slot of the finished set, the running row its hypothesis' last token was
+ *     taken from; it moves with its slot exactly as fin_score / fin_len / fin_flag do (initial state: any value).
+ * With fin_len, a backtrace from fin_parent through parent_log gives the running row that produced every token of a
+ * finished hypothesis: row[n - 1] = fin_parent, row[k - 1] = parent_log[begin_index + k - 1][row[k]]. */
+int kw_beam_select_parents(const kw_beam_select_args* args, int32_t* parent_log, int32_t* fin_parent,
+                           kw_stream_t stream);
+
 /* ---- token-level timestamps (additive, ABI 112 unchanged) --------------------------------------------
  * return_token_timestamps: WhisperGenerationMixin._extract_token_timestamps, _median_filter and
  * _dynamic_time_warping (TF/models/whisper/generation_whisper.py:241-381, 43-61, 64-115) on device.
@@ -575,6 +587,18 @@ int kw_align_capture(int dtype, const void* q, int64_t B, int64_t d, const int32
 int kw_align_weights(int dtype, const void* qlog, int64_t t_log, const void* k_cache, int64_t k_layer_stride,
                      int64_t n_layers, const int32_t* pairs, int64_t A, int64_t B, int64_t H, int64_t S, int64_t T,
                      float* out, kw_stream_t stream);
+
+/* kw_align_weights through a row table (beam search): the log holds R = B * n running rows per pair (item-major),
+ * qlog: [A][R][t_log][64], and step t of item b is the step of log row r = rows[b][t]: its query is qlog[a][r][t] and
+ * its keys are those of r's item, k_cache[layer][r / n] -- item b itself for every step of b's own hypothesis; another
+ * item only where the table names a row of another item (the reference's fall-back to running row 0, TF
+ * generation_whisper.py:287-289).  rows: DEVICE int32 [B][T] with entries in [0, R); an entry outside is clamped into
+ * the range (wrong weights for that step, never a read outside the log or the cache).  out: [A][B][T][S] f32 as above.
+ * Every (step, key) value is computed by kw_align_weights' arithmetic: out[a][b][t] equals, bit for bit, row
+ * [a][rows[b][t]][t] of kw_align_weights run over all R rows (each with its item's keys). */
+int kw_align_weights_rows(int dtype, const void* qlog, int64_t R, int64_t t_log, const int32_t* rows,
+                          const void* k_cache, int64_t k_layer_stride, int64_t n_layers, const int32_t* pairs, int64_t A,
+                          int64_t B, int64_t H, int64_t S, int64_t T, float* out, kw_stream_t stream);
 
 /* weights [A][B][T][S] f32 -> the DTW matrix out [B][T][S] f32: each (a, b, frame) column z-scored over the T steps
  * (population std; a zero std gives NaN as in torch), a median filter of odd filter_width (<= 15) along the frames with

@@ -699,7 +699,12 @@ constexpr int BT = 256;  // beam_select threads
 constexpr int NBMAX = 8;
 constexpr int TMAX = 512;  // history length bound (max_target_positions 448)
 
-__global__ __launch_bounds__(BT) void beam_select_kernel(kw_beam_select_args a) {
+// PAR (kw_beam_select_parents): the step also records who produced what -- plog[L][r] = the running row that next
+// running row r continues, fin_par[b][slot] = the running row a finished hypothesis was taken from (it moves with its
+// slot as fin_score / fin_len / fin_flag do).  Everything else is the plain step, write for write.
+template <bool PAR>
+__device__ __forceinline__ void beam_select_body(const kw_beam_select_args& a, int32_t* __restrict__ plog,
+                                                 int32_t* __restrict__ fin_par) {
   __shared__ float cval[256];
   __shared__ int ckey[256];
   __shared__ float shf[BT / 64];
@@ -711,6 +716,7 @@ __global__ __launch_bounds__(BT) void beam_select_kernel(kw_beam_select_args a) 
   __shared__ int m_key[NBMAX + KMAX];
   __shared__ float old_fs[NBMAX];
   __shared__ int old_fl[NBMAX], old_ff[NBMAX];
+  __shared__ int old_fp[PAR ? NBMAX : 1];
   __shared__ int hist[NBMAX][TMAX];  // parents' token histories (ids < 2^31)
   __shared__ int bph[NBMAX][TMAX];   // parents' slot tables
   __shared__ int fst[NBMAX][TMAX];   // the item's finished rows before this step
@@ -733,6 +739,7 @@ __global__ __launch_bounds__(BT) void beam_select_kernel(kw_beam_select_args a) 
     old_fs[i] = a.fin_score[(int64_t)b * nb + i];
     old_fl[i] = a.fin_len[(int64_t)b * nb + i];
     old_ff[i] = a.fin_flag[(int64_t)b * nb + i];
+    if constexpr (PAR) old_fp[i] = fin_par[(int64_t)b * nb + i];
   }
   // parents' histories (positions < L) and slot tables, before anything is rewritten
   for (int i = tid; i < nb * L; i += BT) {
@@ -826,6 +833,7 @@ __global__ __launch_bounds__(BT) void beam_select_kernel(kw_beam_select_args a) 
     a.fin_score[(int64_t)b * nb + tid] = fs;
     a.fin_len[(int64_t)b * nb + tid] = fl;
     a.fin_flag[(int64_t)b * nb + tid] = ff;
+    if constexpr (PAR) fin_par[(int64_t)b * nb + tid] = src < nb ? old_fp[src] : r0 + t_par[src - nb];
   }
   // 6. running rows: parent history + new token, slot table of the parent + own slot at L
   for (int i = tid; i < nb * (L + 1); i += BT) {
@@ -835,6 +843,9 @@ __global__ __launch_bounds__(BT) void beam_select_kernel(kw_beam_select_args a) 
     if (a.bp) a.bp[(int64_t)(r0 + j) * a.bp_stride + p] = p < L ? bph[t_par[c]][p] : r0 + j;
   }
   if (tid < nb) a.run_scores[r0 + tid] = t_run[run_pos[tid]];
+  if constexpr (PAR) {
+    if (tid < nb) plog[(int64_t)L * ((int64_t)a.B * nb) + r0 + tid] = r0 + t_par[run_pos[tid]];
+  }
   __syncthreads();
   // 7. early-stop heuristic (:3008-3053) at cur_len + 1, and this item's loop-condition inputs
   if (tid == 0) {
@@ -883,6 +894,21 @@ __global__ __launch_bounds__(BT) void beam_select_kernel(kw_beam_select_args a) 
   }
 }
 
+// (one symbol each, PAR a flag of the shared body: the plain launch's code is as it was)
+__global__ __launch_bounds__(BT) void beam_select_kernel(kw_beam_select_args a) {
+  beam_select_body<false>(a, nullptr, nullptr);
+}
+__global__ __launch_bounds__(BT) void beam_select_par_kernel(kw_beam_select_args a, int32_t* plog, int32_t* fin_par) {
+  beam_select_body<true>(a, plog, fin_par);
+}
+
+bool beam_select_args_ok(const kw_beam_select_args* a) {
+  return a && a->B > 0 && a->num_beams >= 2 && a->num_beams <= NBMAX && a->V > 0 && a->cand_val && a->cand_idx &&
+         a->ids && a->run_scores && a->fin_seq && a->fin_score && a->fin_len && a->fin_flag && a->unsat && a->cur_len &&
+         a->counter && a->go && a->done && a->item_flags && a->ids_stride >= a->max_length &&
+         a->fin_stride >= a->max_length && a->max_length <= TMAX && (!a->bp || a->bp_stride >= a->max_length);
+}
+
 }  // namespace
 
 extern "C" size_t kw_beam_logprobs_workspace(int64_t R) {
@@ -922,13 +948,20 @@ extern "C" int kw_beam_logprobs_rep(const kw_beam_logprobs_args* a, float penalt
 }
 
 extern "C" int kw_beam_select(const kw_beam_select_args* a, kw_stream_t stream) {
-  if (!a || a->B <= 0 || a->num_beams < 2 || a->num_beams > NBMAX || a->V <= 0 || !a->cand_val || !a->cand_idx ||
-      !a->ids || !a->run_scores || !a->fin_seq || !a->fin_score || !a->fin_len || !a->fin_flag ||
-      !a->unsat || !a->cur_len || !a->counter || !a->go || !a->done || !a->item_flags ||
-      a->ids_stride < a->max_length || a->fin_stride < a->max_length || a->max_length > TMAX ||
-      (a->bp && a->bp_stride < a->max_length))
+  if (!beam_select_args_ok(a))
     return kw_set_error_msg(KW_EINVAL, "kw_beam_select: invalid arguments (2 <= num_beams <= 8, max_length <= 512)");
   hipLaunchKernelGGL(beam_select_kernel, dim3((unsigned)a->B), dim3(BT), 0, (hipStream_t)stream, *a);
+  KW_CHECK_LAUNCH();
+  return KW_OK;
+}
+
+extern "C" int kw_beam_select_parents(const kw_beam_select_args* a, int32_t* parent_log, int32_t* fin_parent,
+                                      kw_stream_t stream) {
+  if (!beam_select_args_ok(a) || !parent_log || !fin_parent)
+    return kw_set_error_msg(KW_EINVAL, "kw_beam_select_parents: invalid arguments (kw_beam_select's, and both "
+                                       "parent outputs)");
+  hipLaunchKernelGGL(beam_select_par_kernel, dim3((unsigned)a->B), dim3(BT), 0, (hipStream_t)stream, *a, parent_log,
+                     fin_parent);
   KW_CHECK_LAUNCH();
   return KW_OK;
 }

@@ -1,6 +1,8 @@
 // Token-level timestamps (TF/models/whisper/generation_whisper.py:43-115, 241-381) on device:
 //   kw_align_capture   per decode step: the alignment heads' cross-attention queries -> a log [A][B][t_log][64]
 //   kw_align_weights   after decoding: softmax_s(q_t . K[b,h,s,:]) of every logged step, K from the cross cache
+//   kw_align_weights_rows   the same with step t of item b read from log row rows[b][t] (beam search: the running row
+//                      that produced the returned hypothesis' token)
 //   kw_align_reduce    z-score over steps, median filter over frames, mean over heads, negate -> DTW matrix
 //   kw_dtw             dynamic time warping (anti-diagonal wavefront) + backtrace -> frame index of every step
 // The host only turns frame indices into seconds and lays the results out.
@@ -37,6 +39,25 @@ __global__ __launch_bounds__(64) void align_capture_kernel(const T* __restrict__
   log[(((int64_t)a.slot[p] * B + b) * t_log + t) * HD + l] = q[(int64_t)b * d + (int64_t)a.head[p] * HD + l];
 }
 
+// Where a block's WT queries lie: consecutive steps of one log row (kw_align_weights), or every step in a log row of
+// its own, named by a device table (kw_align_weights_rows).  operator()(r): the 64 elements of the block's step r.
+// align_scores takes the steps it computes and writes as a bit set (`steps`): all nt of them for kw_align_weights;
+// kw_align_weights_rows goes once per item whose keys some of the block's steps attend.
+template <typename T>
+struct StepsOfRow {
+  const T* q;  // step t0 of the row
+  __device__ __forceinline__ const T* operator()(int r) const { return q + r * HD; }
+};
+template <typename T>
+struct StepsByTable {
+  const T* log;         // [R][t_log][64] of one pair
+  const int32_t* rows;  // the item's table entries from step t0 on
+  int R, t_log, t0;
+  // (an entry outside [0, R) is clamped: a bad table gives wrong weights, never a read outside the log)
+  __device__ __forceinline__ int row(int r) const { return min(max(rows[r], 0), R - 1); }
+  __device__ __forceinline__ const T* operator()(int r) const { return log + ((int64_t)row(r) * t_log + t0 + r) * HD; }
+};
+
 // K[s][0..63] (f32) into registers
 __device__ __forceinline__ void load_row64(const float* p, float* k) {
 #pragma unroll
@@ -50,7 +71,8 @@ __device__ __forceinline__ void load_row64(const float* p, float* k) {
 // 16 key positions at a time: D = Q K^T by two v_mfma_f32_16x16x32_bf16 over the 64-wide head, both operands straight
 // from global memory (lane l: 8 consecutive elements of row l & 15 at k = 8 (l >> 4), of Q for A and of K for B);
 // D's lane holds column l & 15 (the key position) of rows 4 (l >> 4) .. + 3 (the steps).
-__device__ __forceinline__ void align_scores(const bf16_t* __restrict__ ql, const bf16_t* __restrict__ K, int S, int nt,
+template <typename Q>
+__device__ __forceinline__ void align_scores(const Q& ql, const bf16_t* __restrict__ K, int S, uint32_t steps,
                                              float* __restrict__ o) {
   static_assert(WT == 16, "one MFMA row tile per block");
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, r = lane & 15, g = lane >> 4;
@@ -58,7 +80,7 @@ __device__ __forceinline__ void align_scores(const bf16_t* __restrict__ ql, cons
   bf16x8 qa[2];
 #pragma unroll
   for (int kk = 0; kk < 2; ++kk)
-    qa[kk] = r < nt ? *reinterpret_cast<const bf16x8*>(ql + r * HD + kk * 32 + 8 * g) : zero;
+    qa[kk] = ((steps >> r) & 1) ? *reinterpret_cast<const bf16x8*>(ql(r) + kk * 32 + 8 * g) : zero;
   for (int st = wave; st * 16 < S; st += WTHREADS / 64) {
     const int s = st * 16 + r;
     bf16x8 kb[2];
@@ -71,23 +93,26 @@ __device__ __forceinline__ void align_scores(const bf16_t* __restrict__ ql, cons
     if (s < S) {
 #pragma unroll
       for (int i = 0; i < 4; ++i)
-        if (4 * g + i < nt) o[(int64_t)(4 * g + i) * S + s] = acc[i];
+        if ((steps >> (4 * g + i)) & 1) o[(int64_t)(4 * g + i) * S + s] = acc[i];
     }
   }
 }
 
 // f32 (the parity engine): exact f32 FMAs.  A thread owns key positions s = tid, tid + 256, ...: it takes K[s][0..63]
 // into registers once and dots it with the block's queries (LDS, broadcast reads).
-__device__ __forceinline__ void align_scores(const float* __restrict__ ql, const float* __restrict__ K, int S, int nt,
+template <typename Q>
+__device__ __forceinline__ void align_scores(const Q& ql, const float* __restrict__ K, int S, uint32_t steps,
                                              float* __restrict__ o) {
   __shared__ float qs[WT][HD];
-  for (int i = threadIdx.x; i < WT * HD; i += WTHREADS) qs[i / HD][i % HD] = (i / HD < nt) ? ql[i] : 0.f;
+  for (int i = threadIdx.x; i < WT * HD; i += WTHREADS)
+    qs[i / HD][i % HD] = ((steps >> (i / HD)) & 1) ? ql(i / HD)[i % HD] : 0.f;
   __syncthreads();
   for (int s = threadIdx.x; s < S; s += WTHREADS) {
     float k[HD];
     load_row64(K + (int64_t)s * HD, k);
 #pragma unroll 1  // (rolled: unrolled, the queries' LDS reads are hoisted out of the s loop into > 256 registers)
-    for (int t = 0; t < nt; ++t) {
+    for (int t = 0; t < WT; ++t) {
+      if (!((steps >> t) & 1)) continue;
       float acc = 0.f;
 #pragma unroll
       for (int c = 0; c < HD; ++c) acc = fmaf(qs[t][c], k[c], acc);
@@ -96,18 +121,9 @@ __device__ __forceinline__ void align_scores(const float* __restrict__ ql, const
   }
 }
 
-// grid (ceil(T / WT), B, A): the raw scores of WT steps go to `out`, then a wave per step normalises its row in place
-// (max, exp and sum, divide -- torch's softmax).
-template <typename T>
-__global__ __launch_bounds__(WTHREADS) void align_weights_kernel(const T* __restrict__ qlog, const T* __restrict__ kcache,
-                                                                 int64_t k_layer_stride, PairArgs pairs, int B, int H,
-                                                                 int S, int Tn, int t_log, float* __restrict__ out) {
-  const int t0 = blockIdx.x * WT, b = blockIdx.y, a = blockIdx.z;
-  const int nt = min(WT, Tn - t0);  // steps of this block
-  const T* ql = qlog + (((int64_t)a * B + b) * t_log + t0) * HD;
-  const T* K = kcache + (int64_t)pairs.layer[a] * k_layer_stride + ((int64_t)b * H + pairs.head[a]) * (int64_t)S * HD;
-  float* o = out + (((int64_t)a * B + b) * Tn + t0) * (int64_t)S;
-  align_scores(ql, K, S, nt, o);
+// The raw scores of a block's nt steps lie in `o`: a wave per step normalises its row in place (max, exp and sum,
+// divide -- torch's softmax).
+__device__ __forceinline__ void align_softmax(float* __restrict__ o, int S, int nt) {
   __syncthreads();  // the scores other waves wrote
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   for (int t = wave; t < nt; t += WTHREADS / 64) {
@@ -124,6 +140,49 @@ __global__ __launch_bounds__(WTHREADS) void align_weights_kernel(const T* __rest
     sum = wave_sum(sum);
     for (int s = lane; s < S; s += 64) row[s] = row[s] / sum;
   }
+}
+
+// grid (ceil(T / WT), B, A)
+template <typename T>
+__global__ __launch_bounds__(WTHREADS) void align_weights_kernel(const T* __restrict__ qlog, const T* __restrict__ kcache,
+                                                                 int64_t k_layer_stride, PairArgs pairs, int B, int H,
+                                                                 int S, int Tn, int t_log, float* __restrict__ out) {
+  const int t0 = blockIdx.x * WT, b = blockIdx.y, a = blockIdx.z;
+  const int nt = min(WT, Tn - t0);  // steps of this block
+  const StepsOfRow<T> ql{qlog + (((int64_t)a * B + b) * t_log + t0) * HD};
+  const T* K = kcache + (int64_t)pairs.layer[a] * k_layer_stride + ((int64_t)b * H + pairs.head[a]) * (int64_t)S * HD;
+  float* o = out + (((int64_t)a * B + b) * Tn + t0) * (int64_t)S;
+  align_scores(ql, K, S, (1u << nt) - 1u, o);
+  align_softmax(o, S, nt);
+}
+
+// The same grid; the log has R = B * per rows per pair, item b's step t lies in row rows[b][t] (rows: [B][Tn]) and
+// attends the keys of that row's item, rows[b][t] / per -- item b for the steps of b's own hypothesis, another item
+// only where the reference falls back to running row 0.  The block's steps go item by item (one pass almost always).
+template <typename T>
+__global__ __launch_bounds__(WTHREADS) void align_weights_rows_kernel(const T* __restrict__ qlog,
+                                                                      const int32_t* __restrict__ rows, int R,
+                                                                      const T* __restrict__ kcache, int64_t k_layer_stride,
+                                                                      PairArgs pairs, int B, int H, int S, int Tn,
+                                                                      int t_log, float* __restrict__ out) {
+  const int t0 = blockIdx.x * WT, b = blockIdx.y, a = blockIdx.z;
+  const int nt = min(WT, Tn - t0);
+  const StepsByTable<T> ql{qlog + (int64_t)a * R * t_log * HD, rows + (int64_t)b * Tn + t0, R, t_log, t0};
+  float* o = out + (((int64_t)a * B + b) * Tn + t0) * (int64_t)S;
+  const int per = R / B;
+  uint32_t todo = (1u << nt) - 1u;  // (the table is the same for every thread: the loop is uniform)
+  while (todo) {
+    const int item = ql.row(__builtin_ctz(todo)) / per;
+    uint32_t steps = 0;
+    for (int r = 0; r < nt; ++r)
+      if (((todo >> r) & 1) && ql.row(r) / per == item) steps |= 1u << r;
+    const T* K =
+        kcache + (int64_t)pairs.layer[a] * k_layer_stride + ((int64_t)item * H + pairs.head[a]) * (int64_t)S * HD;
+    align_scores(ql, K, S, steps, o);
+    todo &= ~steps;
+    if (todo) __syncthreads();  // (the f32 path's query tile in LDS is rewritten by the next pass)
+  }
+  align_softmax(o, S, nt);
 }
 
 // torch.sort's order: ascending, NaN last
@@ -310,6 +369,35 @@ extern "C" int kw_align_weights(int dtype, const void* qlog, int64_t t_log, cons
                        k_layer_stride, pa, (int)B, (int)H, (int)S, (int)T, (int)t_log, out);
   else
     hipLaunchKernelGGL(align_weights_kernel<bf16_t>, grid, dim3(WTHREADS), 0, s, (const bf16_t*)qlog,
+                       (const bf16_t*)k_cache, k_layer_stride, pa, (int)B, (int)H, (int)S, (int)T, (int)t_log, out);
+  KW_CHECK_LAUNCH();
+  return KW_OK;
+}
+
+extern "C" int kw_align_weights_rows(int dtype, const void* qlog, int64_t R, int64_t t_log, const int32_t* rows,
+                                     const void* k_cache, int64_t k_layer_stride, int64_t n_layers, const int32_t* pairs,
+                                     int64_t A, int64_t B, int64_t H, int64_t S, int64_t T, float* out,
+                                     kw_stream_t stream) {
+  if (!qlog || !rows || !k_cache || !pairs || !out || A <= 0 || A > R_AMAX || B <= 0 || R <= 0 || R > (1 << 20) ||
+      R % (B > 0 ? B : 1) != 0 ||
+      H <= 0 || S <= 0 || T <= 0 || T > t_log || k_layer_stride < 0 || n_layers <= 0 || B > 65535 ||
+      (dtype != KW_DT_F32 && dtype != KW_DT_BF16) || (uintptr_t)k_cache % 16 != 0 || (uintptr_t)qlog % 16 != 0 ||
+      (uintptr_t)rows % 4 != 0 || (k_layer_stride * (dtype == KW_DT_F32 ? 4 : 2)) % 16 != 0)
+    return kw_set_error_msg(KW_EINVAL, "kw_align_weights_rows: invalid arguments (A <= 32 per launch, 1 <= T <= t_log, "
+                                       "R a multiple of B, 16-B aligned cache)");
+  PairArgs pa;
+  for (int64_t i = 0; i < A; ++i) {
+    if (pairs[2 * i] < 0 || pairs[2 * i] >= n_layers || pairs[2 * i + 1] < 0 || pairs[2 * i + 1] >= H)
+      return kw_set_error_msg(KW_EINVAL, "kw_align_weights_rows: (layer, head) out of range");
+    pa.layer[i] = pairs[2 * i], pa.head[i] = pairs[2 * i + 1];
+  }
+  hipStream_t s = (hipStream_t)stream;
+  dim3 grid((unsigned)((T + WT - 1) / WT), (unsigned)B, (unsigned)A);
+  if (dtype == KW_DT_F32)
+    hipLaunchKernelGGL(align_weights_rows_kernel<float>, grid, dim3(WTHREADS), 0, s, (const float*)qlog, rows, (int)R,
+                       (const float*)k_cache, k_layer_stride, pa, (int)B, (int)H, (int)S, (int)T, (int)t_log, out);
+  else
+    hipLaunchKernelGGL(align_weights_rows_kernel<bf16_t>, grid, dim3(WTHREADS), 0, s, (const bf16_t*)qlog, rows, (int)R,
                        (const bf16_t*)k_cache, k_layer_stride, pa, (int)B, (int)H, (int)S, (int)T, (int)t_log, out);
   KW_CHECK_LAUNCH();
   return KW_OK;

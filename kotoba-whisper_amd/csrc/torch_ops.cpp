@@ -565,16 +565,16 @@ void repeat_process(Tensor& scores, const Tensor& ids, const Tensor& cur_len, do
         w);
 }
 
-// cfg = [B, num_beams, V, begin_index, max_length, eos_id, fill_id, early_stopping]
-void beam_select(const Tensor& cand_val, const Tensor& cand_idx, Tensor& ids, optional<Tensor> bp, Tensor& run_scores,
-                 Tensor& fin_seq, Tensor& fin_score, Tensor& fin_len, Tensor& fin_flag, Tensor& unsat, Tensor& cur_len,
-                 Tensor& counter, Tensor& go, Tensor& done, Tensor& item_flags, std::vector<int64_t> cfg,
-                 double length_penalty) {
-  const char* w = "kw_beam_select";
+// cfg = [B, num_beams, V, begin_index, max_length, eos_id, fill_id, early_stopping]; parent_log / fin_parent: both
+// (kw_beam_select_parents) or neither (kw_beam_select)
+void beam_select_impl(const char* w, const Tensor& cand_val, const Tensor& cand_idx, Tensor& ids, optional<Tensor> bp,
+                      Tensor& run_scores, Tensor& fin_seq, Tensor& fin_score, Tensor& fin_len, Tensor& fin_flag,
+                      Tensor& unsat, Tensor& cur_len, Tensor& counter, Tensor& go, Tensor& done, Tensor& item_flags,
+                      std::vector<int64_t> cfg, double length_penalty, Tensor* parent_log, Tensor* fin_parent) {
   dev(cand_val, w), dev(cand_idx, w), dev(ids, w), dev(bp, w), dev(run_scores, w), dev(fin_seq, w), dev(fin_score, w);
   dev(fin_len, w), dev(fin_flag, w), dev(unsat, w), dev(cur_len, w), dev(counter, w), dev(go, w), dev(done, w);
   dev(item_flags, w);
-  TORCH_CHECK_VALUE(cfg.size() == 8, "kw_beam_select: cfg must hold 8 integers");
+  TORCH_CHECK_VALUE(cfg.size() == 8, w, ": cfg must hold 8 integers");
   kw_beam_select_args a{};
   a.B = cfg[0], a.num_beams = (int32_t)cfg[1], a.V = cfg[2];
   a.cand_val = ptr<const float>(cand_val);
@@ -600,7 +600,33 @@ void beam_select(const Tensor& cand_val, const Tensor& cand_idx, Tensor& ids, op
   a.done = ptr<int32_t>(done);
   a.item_flags = ptr<int32_t>(item_flags);
   c10::DeviceGuard g(ids.device());
-  check(kw_beam_select(&a, stream_of(ids)), w);
+  if (parent_log) {
+    dev(*parent_log, w), dev(*fin_parent, w);
+    TORCH_CHECK_VALUE(parent_log->scalar_type() == at::kInt && parent_log->is_contiguous() &&
+                          parent_log->numel() >= a.max_length * a.B * a.num_beams &&
+                          fin_parent->scalar_type() == at::kInt && fin_parent->is_contiguous() &&
+                          fin_parent->numel() >= a.B * a.num_beams,
+                      w, ": parent_log int32 [max_length][B * num_beams], fin_parent int32 [B][num_beams]");
+    check(kw_beam_select_parents(&a, ptr<int32_t>(*parent_log), ptr<int32_t>(*fin_parent), stream_of(ids)), w);
+  } else {
+    check(kw_beam_select(&a, stream_of(ids)), w);
+  }
+}
+
+void beam_select(const Tensor& cand_val, const Tensor& cand_idx, Tensor& ids, optional<Tensor> bp, Tensor& run_scores,
+                 Tensor& fin_seq, Tensor& fin_score, Tensor& fin_len, Tensor& fin_flag, Tensor& unsat, Tensor& cur_len,
+                 Tensor& counter, Tensor& go, Tensor& done, Tensor& item_flags, std::vector<int64_t> cfg,
+                 double length_penalty) {
+  beam_select_impl("kw_beam_select", cand_val, cand_idx, ids, bp, run_scores, fin_seq, fin_score, fin_len, fin_flag, unsat,
+                   cur_len, counter, go, done, item_flags, cfg, length_penalty, nullptr, nullptr);
+}
+
+void beam_select_parents(const Tensor& cand_val, const Tensor& cand_idx, Tensor& ids, optional<Tensor> bp,
+                         Tensor& run_scores, Tensor& fin_seq, Tensor& fin_score, Tensor& fin_len, Tensor& fin_flag,
+                         Tensor& unsat, Tensor& cur_len, Tensor& counter, Tensor& go, Tensor& done, Tensor& item_flags,
+                         std::vector<int64_t> cfg, double length_penalty, Tensor& parent_log, Tensor& fin_parent) {
+  beam_select_impl("kw_beam_select_parents", cand_val, cand_idx, ids, bp, run_scores, fin_seq, fin_score, fin_len,
+                   fin_flag, unsat, cur_len, counter, go, done, item_flags, cfg, length_penalty, &parent_log, &fin_parent);
 }
 
 // ---- token-level timestamps ---------------------------------------------------------------------------
@@ -640,6 +666,31 @@ void align_weights(const Tensor& qlog, int64_t a0, const Tensor& k_cache, int64_
   check(kw_align_weights(dt_of(qlog), ptr(qlog, a0 * B * qlog.size(2) * 64), qlog.size(2), ptr(k_cache),
                          layer_step * k_cache.stride(0), (k_cache.size(0) + layer_step - 1) / layer_step, p.data(), A, B,
                          H, S, T, ptr<float>(out), stream_of(qlog)),
+        w);
+}
+
+// align_weights with a device row table: qlog [A_all][R][t_log][64], rows int32 [B][T] (entries in [0, R)), k_cache
+// [n_layers'][B][H][S][64]
+void align_weights_rows(const Tensor& qlog, int64_t a0, const Tensor& rows, const Tensor& k_cache, int64_t layer_step,
+                        std::vector<int64_t> pairs, int64_t T, Tensor& out) {
+  const char* w = "kw_align_weights_rows";
+  dev(qlog, w), dev(rows, w), dev(k_cache, w), dev(out, w);
+  const int64_t A = (int64_t)pairs.size() / 2;
+  TORCH_CHECK_VALUE(qlog.dim() == 4 && qlog.is_contiguous() && k_cache.dim() == 5 && k_cache.is_contiguous() &&
+                        k_cache.size(4) == 64 && qlog.size(3) == 64 && k_cache.scalar_type() == qlog.scalar_type() &&
+                        pairs.size() % 2 == 0 && a0 >= 0 && a0 + A <= qlog.size(0) && layer_step >= 1,
+                    "kw_align_weights_rows: qlog [A][R][t_log][64], k_cache [n][B][H][S][64] of one dtype");
+  const int64_t R = qlog.size(1), B = k_cache.size(1), H = k_cache.size(2), S = k_cache.size(3);
+  TORCH_CHECK_VALUE(T > 0 && rows.scalar_type() == at::kInt && rows.is_contiguous() && rows.numel() == B * T,
+                    "kw_align_weights_rows: rows must be a contiguous int32 [B][T] tensor");
+  TORCH_CHECK_VALUE(out.scalar_type() == at::kFloat && out.is_contiguous() && out.numel() >= A * B * T * S,
+                    "kw_align_weights_rows: out must be a contiguous float32 tensor of A * B * T * S elements");
+  const auto p = i32(pairs);
+  c10::DeviceGuard g(qlog.device());
+  check(kw_align_weights_rows(dt_of(qlog), ptr(qlog, a0 * R * qlog.size(2) * 64), R, qlog.size(2),
+                              ptr<const int32_t>(rows), ptr(k_cache), layer_step * k_cache.stride(0),
+                              (k_cache.size(0) + layer_step - 1) / layer_step, p.data(), A, B, H, S, T, ptr<float>(out),
+                              stream_of(qlog)),
         w);
 }
 
@@ -745,6 +796,12 @@ TORCH_LIBRARY(kw, m) {
         "Tensor(d!) fin_seq, Tensor(e!) fin_score, Tensor(f!) fin_len, Tensor(g!) fin_flag, Tensor(h!) unsat, "
         "Tensor(i!) cur_len, Tensor(j!) counter, Tensor(k!) go, Tensor(l!) done, Tensor(m!) item_flags, int[] cfg, "
         "float length_penalty) -> ()");
+  m.def("beam_select_parents(Tensor cand_val, Tensor cand_idx, Tensor(a!) ids, Tensor(b!)? bp, Tensor(c!) run_scores, "
+        "Tensor(d!) fin_seq, Tensor(e!) fin_score, Tensor(f!) fin_len, Tensor(g!) fin_flag, Tensor(h!) unsat, "
+        "Tensor(i!) cur_len, Tensor(j!) counter, Tensor(k!) go, Tensor(l!) done, Tensor(m!) item_flags, int[] cfg, "
+        "float length_penalty, Tensor(n!) parent_log, Tensor(o!) fin_parent) -> ()");
+  m.def("align_weights_rows(Tensor qlog, int a0, Tensor rows, Tensor k_cache, int layer_step, int[] pairs, int T, "
+        "Tensor(a!) out) -> ()");
   m.def("align_capture(Tensor q, int[] heads, int[] slots, Tensor cur_len, int begin_index, Tensor(a!) log) -> ()");
   m.def("align_weights(Tensor qlog, int a0, Tensor k_cache, int layer_step, int[] pairs, int T, Tensor(a!) out) -> ()");
   m.def("align_reduce(Tensor weights, int A, int B, int T, int S, Tensor? frames, int filter_width, Tensor(a!) out, "
@@ -776,6 +833,8 @@ TORCH_LIBRARY_IMPL(kw, CUDA, m) {
   m.impl("beam_logprobs_rep", &beam_logprobs_rep);
   m.impl("repeat_process", &repeat_process);
   m.impl("beam_select", &beam_select);
+  m.impl("beam_select_parents", &beam_select_parents);
+  m.impl("align_weights_rows", &align_weights_rows);
   m.impl("align_capture", &align_capture);
   m.impl("align_weights", &align_weights);
   m.impl("align_reduce", &align_reduce);

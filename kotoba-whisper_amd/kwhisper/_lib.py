@@ -22,7 +22,8 @@ TORCH_LIB_PATH = os.environ.get("KWHISPER_TORCH_LIB") or os.path.join(os.path.di
 TORCH_OPS = ("log_mel", "mel_to_time_major", "gemm", "dec_linear", "pack_weight", "layernorm", "attention", "embed",
              "self_attn_step", "dec_qkv_self", "dec_xq_cross", "cross_attn_step", "greedy_step", "sample_step", "dec_lm_greedy",
              "beam_logprobs", "beam_select", "align_capture", "align_weights", "align_reduce", "dtw", "cross_kv_quant",
-             "cross_attn_step_fp8", "dec_xq_cross_fp8", "self_attn_step_masked", "repeat_process", "beam_logprobs_rep")
+             "cross_attn_step_fp8", "dec_xq_cross_fp8", "self_attn_step_masked", "repeat_process", "beam_logprobs_rep",
+             "beam_select_parents", "align_weights_rows")
 
 KW_OK, KW_EINVAL, KW_EHIP, KW_EUNSUPPORTED = 0, 1, 2, 3
 KW_DT_F32, KW_DT_BF16 = 0, 1
@@ -195,6 +196,9 @@ EXPORTS = {
     "kw_dtw_workspace": (ctypes.c_size_t, [c_i64, c_i64, c_i64]),
     "kw_repeat_process": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, ctypes.c_float, c_i32, c_vp]),
     "kw_beam_logprobs_rep": (ctypes.c_int, [ctypes.POINTER(BeamLogprobsArgs), ctypes.c_float, c_i32, c_vp]),
+    "kw_beam_select_parents": (ctypes.c_int, [ctypes.POINTER(BeamSelectArgs), c_vp, c_vp, c_vp]),
+    "kw_align_weights_rows": (ctypes.c_int, [ctypes.c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64,
+                                             ctypes.POINTER(c_i32), c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp]),
 }
 
 _lib = None

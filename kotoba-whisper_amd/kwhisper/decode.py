@@ -267,7 +267,7 @@ class DecodeSession:
 
     def _step_plans(self, q: int, fused: bool = False, align=None, begin_index: int = 0, masked: bool = False):
         """The decoder forward for q new positions per row (q = prompt length for the prefill, 1 after).
-        ``align`` (q == 1, greedy): the alignment (layer, head) pairs whose cross-attention queries every step logs
+        ``align`` (q == 1): the alignment (layer, head) pairs whose cross-attention queries every step logs
         (kw_align_capture after the layer's query projection; such a layer takes the two-launch cross path, which
         leaves the query in global memory and is bitwise the fused block).  None: exactly the plain plan.
         ``fused`` (q == 1): each layer's LayerNorm-fused QKV projection and self-attention step as ONE
@@ -540,7 +540,7 @@ class DecodeSession:
             if not align or any(not (0 <= l < nl and 0 <= h < nh) for l, h in align):
                 raise ValueError(f"alignment_heads must be [layer, head] pairs within {nl} layers x {nh} heads")
             if self.nb != 1:
-                raise NotImplementedError("token timestamps with beam search")
+                raise NotImplementedError("token timestamps on a beam session go through generate_beam(align=...)")
             if self.fp8:
                 raise NotImplementedError("token timestamps with cross_kv_dtype='fp8_e4m3' (kw_align_weights reads the "
                                           "bf16 K cache)")
@@ -761,8 +761,10 @@ class DecodeSession:
             logits = self.forward_logits(torch.full((self.B, 1), sot, dtype=torch.int64, device=self.eng.device))
         return torch.softmax(logits.float(), -1)[:, token].cpu().numpy().astype(np.float64)
 
-    def _alignment(self, align, T: int, num_frames, width: int):
-        """weights -> reduce -> DTW over the first ``T`` logged steps; the host receives (B, T) frame indices."""
+    def _alignment(self, align, T: int, num_frames, width: int, rows=None):
+        """weights -> reduce -> DTW over the first ``T`` logged steps; the host receives (B, T) frame indices.
+        ``rows`` (beam search): host int (B, T), the log row -- the running row -- that holds step t of item b
+        (kw_align_weights_rows); None: item b's steps are log row b's (kw_align_weights)."""
         B, S, dev = self.B, self.T, self.eng.device
         if T <= 0:
             return dict(frames=np.zeros((B, 0), np.int32), T=0)
@@ -772,6 +774,11 @@ class DecodeSession:
             # the reference crops with weights[..., : n // 2] (generation_whisper.py:354): a Python slice, so a
             # negative n (a row whose mask ends before the pass's seek) keeps S + n // 2 positions
             frames = torch.tensor([len(range(S)[: int(n) // 2]) for n in num_frames], dtype=torch.int32, device=dev)
+        if rows is not None:
+            rows = np.ascontiguousarray(rows, dtype=np.int32)
+            if rows.shape != (B, T) or (rows < 0).any() or (rows >= self.R).any():
+                raise ValueError(f"the alignment row table must be (B, T) with entries in [0, {self.R})")
+            rows = torch.from_numpy(rows).to(dev)
         A = len(align)
         # pairs per chunk: the f32 weights of a chunk stay under 256 MB (and 32 pairs, the kernels' launch limit)
         chunk = max(1, min(32, A, (256 << 20) // (B * T * S * 4)))
@@ -780,7 +787,10 @@ class DecodeSession:
         kept = []
         for a0 in range(0, A, chunk):
             n = min(chunk, A - a0)
-            ops.align_weights(log, self.cross, align[a0: a0 + n], T, weights, a0=a0, layer_step=2)
+            if rows is None:
+                ops.align_weights(log, self.cross, align[a0: a0 + n], T, weights, a0=a0, layer_step=2)
+            else:
+                ops.align_weights_rows(log, rows, self.cross, align[a0: a0 + n], T, weights, a0=a0, layer_step=2)
             ops.align_reduce(weights, n, B, T, S, frames, width, matrix, a_total=A, first=a0 == 0, last=a0 + n >= A)
             if self.keep_alignment:
                 kept.append(weights[:n].clone())
@@ -795,7 +805,7 @@ class DecodeSession:
 
     def generate_beam(self, prompt: torch.Tensor, gen, *, num_beams: int, max_length: int, return_timestamps: bool,
                       length_penalty: float = 1.0, early_stopping=False, check_every: int = 4, use_graph: bool = True,
-                      repeat=None):
+                      repeat=None, align=None, num_frames=None, median_filter_width: int = 7):
         """``GenerationMixin._beam_search`` (TF/generation/utils.py:3208-3527) on device, num_return_sequences 1.
 
         ``prompt`` (B, P) per item.  Returns host int64 (B, P + generated) -- the best finished beam of each
@@ -803,11 +813,25 @@ class DecodeSession:
 
         ``repeat``: (repetition_penalty, no_repeat_ngram_size), or None.  None or (1.0, 0): exactly today's plan and
         graphs.  Otherwise kw_beam_logprobs_rep takes kw_beam_logprobs' place: both processors act on every row's
-        log-probs, from the row's own re-ordered history, before the Whisper processors."""
+        log-probs, from the row's own re-ordered history, before the Whisper processors.
+
+        ``align``, ``num_frames``, ``median_filter_width``: token timestamps, as in ``generate``.  None: exactly today's
+        plan, graph keys and launches.  Otherwise every step logs the alignment heads' queries of all R running rows,
+        the selection is kw_beam_select_parents (which also records every step's parents), and after the search the
+        host backtraces the returned hypotheses to the reference's ``beam_indices`` (``beam_backtrace``), turns them
+        into the row table of TF generation_whisper.py:265-301 (``beam_row_table``) and the alignment stage reads the
+        log through it (kw_align_weights_rows).  ``self.align_out`` is laid out as the greedy path's -- ``frames``
+        int32 (B, W - 1), W the longest returned hypothesis in generated tokens -- plus ``beam_indices`` (B, W)."""
         repeat = _norm_repeat(repeat)
         B, nb, R = self.B, self.nb, self.R
         if nb != num_beams or nb < 2:
             raise ValueError("session beam width mismatch")
+        if align is not None:
+            align = tuple((int(l), int(h)) for l, h in align)
+            nl, nh = self.eng.shape.decoder_layers, self.eng.H
+            if not align or any(not (0 <= l < nl and 0 <= h < nh) for l, h in align):
+                raise ValueError(f"alignment_heads must be [layer, head] pairs within {nl} layers x {nh} heads")
+        self.align_out = None
         P = prompt.shape[1]
         if max_length > T_MAX:
             raise ValueError(f"max_length {max_length} exceeds max_target_positions {T_MAX}")
@@ -825,6 +849,8 @@ class DecodeSession:
                gen.no_timestamps_token_id, gen.eos_token_id, gen.max_initial_timestamp_index)
         if repeat is not None:
             key += (("repeat",) + repeat,)
+        if align is not None:
+            key += (("align",) + align,)
         cfg = self._greedy_cfg.get(key)
         if cfg is None:
             st = dict(
@@ -843,6 +869,9 @@ class DecodeSession:
                 cand_idx=torch.empty((R, 2 * nb), device=dev, dtype=torch.int32),
                 lp_ws=torch.zeros(((ops.beam_logprobs_workspace_bytes(R) + 3) // 4,), device=dev, dtype=torch.float32),
             )
+            if align is not None:  # (their presence selects kw_beam_select_parents)
+                st["parent_log"] = torch.zeros((max_length, R), device=dev, dtype=torch.int32)
+                st["fin_parent"] = torch.zeros((B, nb), device=dev, dtype=torch.int32)
             sup = torch.zeros((V,), dtype=torch.uint8)
             if gen.suppress_tokens:
                 sup[torch.tensor(gen.suppress_tokens)] = 1
@@ -870,13 +899,16 @@ class DecodeSession:
         st["go"].fill_(1)
         st["done"].zero_()
         st["item_flags"].zero_()
+        if align is not None:
+            st["parent_log"].zero_()
+            st["fin_parent"].fill_(-1)
         self._beam_state = st
 
         def prefill():
             self._run(self._step_plans(P))  # prefill on every running row (the reference expands x num_beams)
             step()
 
-        step_seq = self._step_plans(1)
+        step_seq = self._step_plans(1) if align is None else self._step_plans(1, align=align, begin_index=P)
 
         def one_step():
             self._run(step_seq)
@@ -908,7 +940,43 @@ class DecodeSession:
         self.check_handoffs()
         fin_len = st["fin_len"][:, 0].cpu().numpy()
         out = st["fin_seq"][:, 0].cpu().numpy()
+        if align is not None:
+            bi = beam_backtrace(st["parent_log"].cpu().numpy(), st["fin_parent"][:, 0].cpu().numpy(), fin_len, P)
+            table = beam_row_table(bi)
+            self.align_out = self._alignment(align, table.shape[1], num_frames, median_filter_width, rows=table)
+            self.align_out["beam_indices"] = bi
         return out[:, : P + int(fin_len.max())]
+
+
+def beam_backtrace(parent_log: np.ndarray, fin_parent: np.ndarray, fin_len: np.ndarray, begin_index: int) -> np.ndarray:
+    """The reference's ``beam_indices`` of the returned hypotheses from what kw_beam_select_parents recorded.
+
+    ``parent_log`` (max_length, R): row L, written by the step at cur_len = L, names for every next running row the
+    running row it continues.  ``fin_parent`` (B,): the running row the returned hypothesis' last token was taken
+    from, ``fin_len`` (B,) its generated tokens.  Returns int32 (B, W), W = the longest hypothesis: entry k is the
+    running row whose logits gave generated token k, -1 beyond the hypothesis' own length."""
+    fin_len = np.asarray(fin_len, dtype=np.int64)
+    B, W = len(fin_len), int(fin_len.max()) if len(fin_len) else 0
+    out = np.full((B, W), -1, dtype=np.int32)
+    for b in range(B):
+        n = int(fin_len[b])
+        if n == 0:
+            continue
+        r = int(fin_parent[b])
+        out[b, n - 1] = r
+        for k in range(n - 1, 0, -1):  # the row that gave token k held, after the step before, the history of ...
+            r = int(parent_log[begin_index + k - 1, r])
+            out[b, k - 1] = r
+    return out
+
+
+def beam_row_table(beam_indices: np.ndarray) -> np.ndarray:
+    """(B, W) ``beam_indices`` -> int32 (B, W - 1): the running row whose cross-attention the reference reads for
+    step j of returned row b (TF generation_whisper.py:265-301 once the prompt positions are cut): the row that gave
+    token j + 1, and running row 0 of the whole batch where the hypothesis has ended (-1)."""
+    bi = np.asarray(beam_indices)
+    t = bi[:, 1:].astype(np.int32)
+    return np.where(t == -1, 0, t).astype(np.int32)
 
 
 def _norm_repeat(repeat):

@@ -78,6 +78,10 @@ class WhisperEngine:
             raise ValueError("cross_kv_dtype='fp8_e4m3' needs dtype=torch.bfloat16 (the packed-weight decode path)")
         self.cross_kv_dtype = cross_kv_dtype
         self.cross_kv_fp8 = cross_kv_dtype == "fp8_e4m3"
+        # this engine's beam sessions serve return_token_timestamps (DecodeSession.generate_beam(align=...):
+        # kw_beam_select_parents, kw_align_weights_rows); generate() refuses the combination, before anything touches
+        # the device, on an engine object that does not say so.  Not with the fp8 cache, which has no beam kernel.
+        self.beam_token_ts = not self.cross_kv_fp8
         L.load()
         L.load_torch_ops()  # torch.ops.kw.* (the launch path of every op); raises if it was not built
         self.shape = shape

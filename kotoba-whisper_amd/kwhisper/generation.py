@@ -16,6 +16,11 @@ TF/models/whisper/generation_whisper.py:383-968):
   * ``num_beams`` > 1: GenerationMixin._beam_search on device (TF/generation/utils.py:3208-3527)
   * ``return_token_timestamps``: the alignment heads' cross-attention weights, their normalisation and the
     dynamic time warping on device (csrc/token_ts.hip)                :241-381, :1146-1157, :1685-1700
+    -- with ``num_beams`` > 1 too: every running row's queries are logged, the beam step records its parents
+    (kw_beam_select_parents), the host backtraces the returned hypotheses to ``beam_indices`` and the weights are read
+    through that table (kw_align_weights_rows); a row shorter than the pass's longest reads running row 0 of the
+    pass for its remaining steps, as the reference does                :265-301
+    (not together with the fallback, prompts or the fp8 cross cache; asked of the engine, ``beam_token_ts``)
   * the decoding fallback -- ``temperature`` (a float or a schedule), ``compression_ratio_threshold``,
     ``logprob_threshold``, ``no_speech_threshold``: per seek pass the attempt loop of ``generate_with_fallback``, every
     row's ``_need_fallback`` decision, the no-speech skip; tokens drawn and log-probabilities accumulated on device
@@ -307,10 +312,13 @@ class KWhisperForConditionalGeneration:
                     "Model generation config has no `alignment_heads`, token-level timestamps not available. "
                     "See https://gist.github.com/hollance/42e32852f24243b748ae6bc1f985b13a on how to add this property "
                     "to the generation config.")
-            if num_beams > 1:
+            if num_beams > 1 and not getattr(self.engine, "beam_token_ts", False):
+                # (asked of the engine before anything touches the device, like the fp8 checks above: beam sessions
+                # that log every running row's queries and record the beam parents are WhisperEngine.beam_token_ts)
                 raise NotImplementedError(
-                    "`return_token_timestamps` with `num_beams` > 1 is not supported by the MI355X engine yet (the "
-                    "beam_indices gather of the cross-attention weights); use greedy decoding")
+                    "`return_token_timestamps` with `num_beams` > 1 needs an engine whose beam sessions keep the "
+                    "alignment log and the beam parents (`beam_token_ts`), which this engine does not declare; use "
+                    "greedy decoding")
             align = [tuple(p) for p in gen.alignment_heads]
             if attention_mask is not None:
                 ts_frames = torch.as_tensor(attention_mask).sum(-1).cpu().long().numpy()
@@ -458,7 +466,7 @@ class KWhisperForConditionalGeneration:
                 for rec in attempts:  # (:1088-1093): a row accepted at a temperature of 0.5 or more loses its conditioning
                     for p in rec["rows"]:
                         do_condition[p] = cond_prev and rec["temperature"] < 0.5
-            elif num_beams > 1:
+            elif num_beams > 1 and not token_ts:
                 ids = sess.generate_beam(torch.from_numpy(prompt), gen, num_beams=num_beams, max_length=eff_max,
                                          return_timestamps=return_timestamps, length_penalty=length_penalty,
                                          early_stopping=early_stopping, **rep_kw)
@@ -466,9 +474,15 @@ class KWhisperForConditionalGeneration:
                 # per pass: num_frames - seek of the rows still running (generation_whisper.py:1146-1150)
                 nf = None if ts_frames is None else [int(ts_frames[p] - seek[p]) for p in batch_map]
                 sess.keep_alignment = self.record_alignment
-                ids = sess.generate(torch.from_numpy(prompt), gen, max_length=eff_max,
-                                    return_timestamps=return_timestamps, align=align, num_frames=nf,
-                                    median_filter_width=s.median_filter_width, **rep_kw)
+                ts_kw = dict(rep_kw, max_length=eff_max, return_timestamps=return_timestamps, align=align, num_frames=nf,
+                             median_filter_width=s.median_filter_width)
+                if num_beams > 1:
+                    # the returned hypotheses' steps are gathered from the running rows that produced them
+                    # (beam_indices, generation_whisper.py:265-301); every row gets P + longest hypothesis times
+                    ids = sess.generate_beam(torch.from_numpy(prompt), gen, num_beams=num_beams,
+                                             length_penalty=length_penalty, early_stopping=early_stopping, **ts_kw)
+                else:
+                    ids = sess.generate(torch.from_numpy(prompt), gen, **ts_kw)
                 pass_ts = _pass_token_timestamps(sess.align_out["frames"], P, ids.shape[1])
                 if self.record_alignment:
                     align_log.append(dict(sess.align_out, rows=[int(p) for p in batch_map], num_input_ids=P))

@@ -796,7 +796,9 @@ class RepeatPlan:
 
 class BeamStepPlan:
     """Pre-built ``kw_beam_logprobs`` + ``kw_beam_select`` calls for one beam-search step.  ``repeat`` = (penalty,
-    ngram): ``kw_beam_logprobs_rep`` takes ``kw_beam_logprobs``'s place (None: exactly the plain launch)."""
+    ngram): ``kw_beam_logprobs_rep`` takes ``kw_beam_logprobs``'s place (None: exactly the plain launch).  A state
+    that holds ``parent_log`` (int32 [max_length][R]) and ``fin_parent`` (int32 [B][nb]) selects
+    ``kw_beam_select_parents``, which also fills those two; without them the launch is ``kw_beam_select``."""
 
     def __init__(self, st, logits, suppress_mask, begin_suppress, *, return_timestamps, ts_begin, no_ts_id, eos_id,
                  max_initial_ts, begin_index, max_length, fill_id, length_penalty, early_stopping, repeat=None):
@@ -846,6 +848,28 @@ class BeamStepPlan:
         b.item_flags = st["item_flags"].data_ptr()
         self.a, self.b = a, b
         self._ra, self._rb = ctypes.byref(a), ctypes.byref(b)
+        plog, fpar = st.get("parent_log"), st.get("fin_parent")
+        if (plog is None) != (fpar is None):
+            raise ValueError("beam step: parent_log and fin_parent go together")
+        self._par = None
+        if plog is not None:
+            _cuda(plog, fpar)
+            if (plog.dtype != torch.int32 or fpar.dtype != torch.int32 or not plog.is_contiguous()
+                    or not fpar.is_contiguous() or plog.numel() < max_length * R or fpar.numel() < B * nb):
+                raise ValueError("beam step: parent_log int32 [max_length][R], fin_parent int32 [B][num_beams]")
+            self._par = (plog, fpar)
+
+    def _select(self):
+        if self._par is None:
+            if _BACKEND == "torch":
+                _kw().beam_select(*self._tsel)
+            else:
+                L.check(_lib().kw_beam_select(self._rb, _s()), "kw_beam_select")
+        elif _BACKEND == "torch":
+            _kw().beam_select_parents(*self._tsel, *self._par)
+        else:
+            L.check(_lib().kw_beam_select_parents(self._rb, _p(self._par[0]), _p(self._par[1]), _s()),
+                    "kw_beam_select_parents")
 
     def __call__(self):
         if _BACKEND == "torch":
@@ -854,13 +878,12 @@ class BeamStepPlan:
                 kw.beam_logprobs(*self._tlp)
             else:
                 kw.beam_logprobs_rep(*self._tlp, *self._rep)
-            kw.beam_select(*self._tsel)
         else:
             if self._rep is None:
                 L.check(_lib().kw_beam_logprobs(self._ra, _s()), "kw_beam_logprobs")
             else:
                 L.check(_lib().kw_beam_logprobs_rep(self._ra, self._rep[0], self._rep[1], _s()), "kw_beam_logprobs_rep")
-            L.check(_lib().kw_beam_select(self._rb, _s()), "kw_beam_select")
+        self._select()
 
 
 # ---- token-level timestamps (csrc/token_ts.hip) ------------------------------------------------------------------
@@ -914,6 +937,32 @@ def align_weights(qlog, k_cache, pairs, T, out, a0=0, layer_step=1):
     L.check(_lib().kw_align_weights(_dt(qlog), q0, t_log, _p(k_cache), layer_step * k_cache.stride(0),
                                     (k_cache.shape[0] + layer_step - 1) // layer_step, _i32s(flat), A, B, H, S, int(T),
                                     _p(out), _s()), "kw_align_weights")
+    return out
+
+
+def align_weights_rows(qlog, rows, k_cache, pairs, T, out, a0=0, layer_step=1):
+    """``align_weights`` through a row table: the log holds R = B * n running rows per pair (``qlog``
+    [A][R][t_log][64]) and step t of item b is the step of log row ``rows[b][t]`` (device int32 [B][T], entries in
+    [0, R); the kernel clamps an entry outside): that row's query over the keys of that row's item,
+    ``k_cache`` [n][B][H][S][64] at item ``rows[b][t] // n``.  ``out`` [A][B][T][S] f32."""
+    _cuda(qlog, rows, k_cache, out)
+    flat = [int(v) for p in pairs for v in p]
+    if _BACKEND == "torch":
+        _kw().align_weights_rows(qlog, int(a0), rows, k_cache, int(layer_step), flat, int(T), out)
+        return out
+    A = len(pairs)
+    if (qlog.dim() != 4 or k_cache.dim() != 5 or not qlog.is_contiguous() or not k_cache.is_contiguous()
+            or k_cache.dtype != qlog.dtype or a0 < 0 or a0 + A > qlog.shape[0] or T <= 0 or rows.dtype != torch.int32
+            or not rows.is_contiguous() or rows.numel() != k_cache.shape[1] * T or out.dtype != torch.float32
+            or not out.is_contiguous() or out.numel() < A * k_cache.shape[1] * T * k_cache.shape[3]):
+        raise ValueError("align_weights_rows: qlog [A][R][t_log][64], rows int32 [B][T], k_cache [n][B][H][S][64], "
+                         "out f32 [A][B][T][S]")
+    R, t_log = qlog.shape[1], qlog.shape[2]
+    B, H, S = k_cache.shape[1], k_cache.shape[2], k_cache.shape[3]
+    q0 = ctypes.c_void_p(qlog.data_ptr() + a0 * R * t_log * 64 * qlog.element_size())
+    L.check(_lib().kw_align_weights_rows(_dt(qlog), q0, R, t_log, _p(rows), _p(k_cache), layer_step * k_cache.stride(0),
+                                         (k_cache.shape[0] + layer_step - 1) // layer_step, _i32s(flat), A, B, H, S,
+                                         int(T), _p(out), _s()), "kw_align_weights_rows")
     return out
 
 

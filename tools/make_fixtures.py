@@ -931,6 +931,104 @@ def token_ts_fixtures():
     print(f"token_ts fixtures done: {n_stable}/{n_all} stable ({time.time() - t0:.1f}s)")
 
 
+# ---- token timestamps under beam search (tests/golden/beam_ts_tiny.npz) ------------------------------------------
+# name -> (generate kwargs, eos override as in BEAM_MODES)
+BEAM_TS_MODES = {
+    "b3": (dict(return_timestamps=False, num_beams=3, max_length=40), 7656),
+    "b3_ts": (dict(return_timestamps=True, num_beams=3, max_length=40), 7656),
+    "b4_lp_es": (dict(return_timestamps=False, num_beams=4, max_length=40, length_penalty=0.5, early_stopping=True), 7656),
+    "b2": (dict(return_timestamps=False, num_beams=2, max_length=24), None),
+}
+
+
+def _beam_ts_run(m, feats, mask, heads, eos, **kw):
+    gconf, _ = hf_gen_config(TINY)
+    gconf.alignment_heads = heads
+    if eos is not None:
+        gconf.eos_token_id = eos
+    m.generation_config = gconf
+    rec = _TokenTsRecorder(m)
+    try:
+        with torch.no_grad():
+            res = m.generate(feats, attention_mask=mask, language="ja", task="transcribe", return_token_timestamps=True,
+                             return_segments=True, **kw)
+    finally:
+        rec.close()
+    return res, rec
+
+
+def _beam_gathered(p):
+    """The weights ``_extract_token_timestamps`` runs its DTW over in a beam pass: [rows][A][W - 1][S], step j of
+    returned row b from running row ``beam_indices[b][j + 1]`` (-1 -> running row 0), W the longest hypothesis."""
+    bi = p["outs"].beam_indices.numpy()
+    W = int((bi != -1).sum(-1).max())
+    w = p["weights"]  # [R][A][forwards past the prompt][S]
+    idx = np.where(bi[:, 1:W] == -1, 0, bi[:, 1:W])
+    return np.stack([w[idx[:, j], :, j] for j in range(W - 1)], axis=2) if W > 1 else w[: len(bi), :, :0], bi[:, :W]
+
+
+def beam_ts_fixtures():
+    t0 = time.time()
+    feats = features(TINY.num_mel_bins, TOKEN_TS_CLIPS)
+    mask = torch.ones((feats.shape[0], feats.shape[-1]), dtype=torch.long)
+    for r, n in TOKEN_TS_MASK.items():
+        mask[r, n:] = 0
+    out = {"cases": np.array([f"{k}:{s}" for k, s in TOKEN_TS_CLIPS]), "alignment_heads": np.array(TOKEN_TS_HEADS),
+           "attention_frames": mask.sum(-1).numpy(), "tstride": TOKEN_TS_TSTRIDE, "sstride": TOKEN_TS_SSTRIDE,
+           "modes": np.array(list(BEAM_TS_MODES))}
+    m32, m64 = hf_model(TINY), hf_model(TINY).double()
+    n_stable = n_all = 0
+    any_short = any_switch = False
+    for name, (kw, eos) in BEAM_TS_MODES.items():
+        res, rec = _beam_ts_run(m32, feats, mask, TOKEN_TS_HEADS, eos, **kw)
+        res64, rec64 = _beam_ts_run(m64, feats.double(), mask, TOKEN_TS_HEADS, eos, **kw)
+        assert torch.equal(res["sequences"], res64["sequences"]) and len(rec.passes) == len(rec64.passes)
+        out[f"{name}_kw"] = json.dumps(kw)
+        out[f"{name}_eos"] = -1 if eos is None else eos
+        out[f"{name}_sequences"] = res["sequences"].numpy().astype(np.int64)
+        out[f"{name}_token_timestamps"] = res["token_timestamps"].numpy().astype(np.float32)
+        out[f"{name}_passes"] = len(rec.passes)
+        for b, row in enumerate(res["segments"]):
+            out[f"{name}_seg_len_{b}"] = np.array([len(g["tokens"]) for g in row], dtype=np.int64)
+            out[f"{name}_seg_tts_{b}"] = (np.concatenate([g["token_timestamps"].numpy() for g in row]).astype(np.float32)
+                                         if row else np.zeros(0, np.float32))
+        for i, (p, p64) in enumerate(zip(rec.passes, rec64.passes)):
+            assert np.array_equal(p["sequences"], p64["sequences"]) and p["rows"] == p64["rows"]
+            (w, bi), (w64, bi64) = _beam_gathered(p), _beam_gathered(p64)
+            assert np.array_equal(bi, bi64), (name, i)
+            assert p["ts"].shape == (len(p["rows"]), p["P"] + bi.shape[1]), (p["ts"].shape, p["P"], bi.shape)
+            lens = (bi != -1).sum(-1)
+            # the agreed region of the row-0 rule: the pass's first item is among the longest
+            assert lens[0] == lens.max(), f"{name} pass {i}: item 0 is not among the longest {lens.tolist()}: pick other clips"
+            nb = kw["num_beams"]
+            any_short |= bool((lens < lens.max()).any())
+            any_switch |= any(len(set((bi[b, : lens[b]] - b * nb).tolist())) > 1 for b in range(len(bi)))
+            sm = (slice(None), slice(None), slice(None, None, TOKEN_TS_TSTRIDE), slice(None, None, TOKEN_TS_SSTRIDE))
+            ws, ws64 = w[sm], w64[sm]
+            eps = float((np.abs(ws.astype(np.float64) - ws64).max(-1) / ws64.max(-1)).max()) if ws.size else 0.0
+            out[f"{name}_p{i}_rows"] = np.array(p["rows"])
+            out[f"{name}_p{i}_P"] = p["P"]
+            out[f"{name}_p{i}_num_frames"] = p["num_frames"]
+            out[f"{name}_p{i}_sequences"] = p["sequences"].astype(np.int64)
+            out[f"{name}_p{i}_beam_indices"] = bi.astype(np.int32)
+            out[f"{name}_p{i}_ts"] = p["ts"].astype(np.float32)
+            out[f"{name}_p{i}_w32"] = ws.astype(np.float32)
+            out[f"{name}_p{i}_w64"] = ws64.astype(np.float64)
+            out[f"{name}_p{i}_eps_ref"] = eps
+            stable = np.ones(len(p["rows"]), dtype=bool)
+            for d in range(TOKEN_TS_DRAWS):
+                stable &= (rec.perturbed(p, TOKEN_TS_NOISE * eps, 1000 * i + d) == p["ts"]).all(-1)
+            out[f"{name}_p{i}_stable"] = stable
+            n_stable, n_all = n_stable + int(stable.sum()), n_all + stable.size
+            print(f"  beam_ts {name} pass {i}: rows {p['rows']} lengths {lens.tolist()} eps_ref {eps:.2e} "
+                  f"stable {stable.tolist()}")
+    assert any_short, "no committed pass has a row shorter than its longest: pick other clips"
+    assert any_switch, "no committed pass has a beam switch inside a returned hypothesis: pick other clips"
+    assert 4 * n_stable >= 3 * n_all, f"only {n_stable} of {n_all} (pass, row) cases are stable: pick other clips"
+    np.savez_compressed(os.path.join(GOLD, "beam_ts_tiny.npz"), **out)
+    print(f"beam_ts fixtures done: {n_stable}/{n_all} stable ({time.time() - t0:.1f}s)")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--skip-large", action="store_true")
@@ -963,6 +1061,8 @@ def main():
         beam_fixtures()
     if a.only in (None, "token_ts"):
         token_ts_fixtures()
+    if a.only in (None, "beam_ts"):
+        beam_ts_fixtures()
     if a.only in (None, "fallback"):
         fallback_fixtures()
     if a.only in (None, "longform"):
