@@ -471,6 +471,57 @@ typedef struct {
 int kw_sample_step(const kw_sample_args* args, kw_stream_t stream);
 size_t kw_sample_step_workspace(int64_t B);
 
+/* ---- speculative decoding: the accept step (additive, ABI 112 unchanged) -------------------------------
+ * One launch per round, for ONE row (generate(assistant_model=...), batch size 1).  An assistant decoder has drafted K
+ * tokens into ids[L, L + K), L = *cur_len of the main decoder; the main decoder's forward over the K + 1 newest
+ * positions left logits [K + 1][V] (f32), row j predicting position L + j.  For j = 0 .. K the launch computes t_j, the
+ * token kw_greedy_step would choose at *cur_len = L + j with the history ids[0, L + j) -- the drafts before j in
+ * place, so a draft that closes a timestamp pair or shifts the probability-mass rule acts on the positions behind it.
+ * The processors are kw_greedy_step's (SuppressTokens, SuppressTokensAtBegin at L + j == begin_index,
+ * WhisperTimeStamp), each position is split over workgroups as there, ties go to the first index: t_j equals
+ * kw_greedy_step's token (with a workspace) bit for bit.  Then, q running from 0:
+ *   L + q >= max_length: the row is finished, nothing is written at or beyond max_length;
+ *   q < K and ids[L + q] == t_q: the draft is accepted (n += 1); an accepted EOS, or L + q + 1 >= max_length,
+ *     finishes the row; otherwise go on with q + 1;
+ *   else ids[L + q] = t_q -- the correction, or at q == K the bonus token -- which finishes the row if it is EOS or
+ *     L + q + 1 >= max_length; stop.
+ * new length = the position after the last token kept.  A finished row: ids[new length, min(L + K + 1, max_length))
+ * = pad_id, *unfinished = 0, *n_unfinished = 0 (else 1).  Device state written (plain stores by one thread):
+ *   *cur_len = new length; *asst_cur_len = new length and *asst_unfinished = 1 (the assistant may have drafted an
+ *   EOS) where given; *verify_len = new length + K (the cur_len the next round's K + 1-position forward reads) where
+ *   given; stats[0] += 1 (rounds), stats[1] += K (drafted), stats[2] += n (accepted) where given.
+ * *unfinished == 0 at entry: the launch decides nothing and leaves ids, lengths, flags and stats as they are (replays
+ * behind the host's poll are harmless); it only puts *asst_cur_len back to *cur_len, so an assistant that keeps
+ * drafting behind a finished row never moves further than K + 1 positions past the final length.
+ * workspace: REQUIRED, >= kw_spec_accept_workspace(K) bytes (0 for an unsupported K), zero-filled once; every launch
+ * leaves it all zero.  1 <= K <= 31; max_length <= ids_stride. */
+typedef struct {
+  const float* logits;        /* [K + 1][V] f32 raw logits of positions L .. L + K */
+  int64_t V;
+  int32_t K;
+  const uint8_t* suppress_mask;
+  const int32_t* begin_suppress;
+  int32_t n_begin_suppress;
+  int32_t return_timestamps;
+  int32_t ts_begin, no_ts_id, eos_id, pad_id;
+  int32_t max_initial_ts;     /* -1 = None */
+  int64_t* ids;               /* [ids_stride]: the row */
+  int64_t ids_stride;
+  int32_t* cur_len;           /* [1] the main decoder's */
+  int32_t max_length, begin_index;
+  int32_t* unfinished;        /* [1] */
+  int32_t* n_unfinished;      /* [1] */
+  int32_t* asst_cur_len;      /* [1] or NULL */
+  int32_t* asst_unfinished;   /* [1] or NULL */
+  int32_t* verify_len;        /* [1] or NULL */
+  int32_t* stats;             /* [3] rounds, drafted, accepted; or NULL */
+  void* workspace;
+  size_t ws_bytes;
+} kw_spec_accept_args;
+
+int kw_spec_accept(const kw_spec_accept_args* args, kw_stream_t stream);
+size_t kw_spec_accept_workspace(int64_t K);
+
 /* ---- beam search step (a10: TF/generation/utils.py:3208-3527), num_return_sequences = 1 ----------
  * Running rows are R = B * num_beams, item-major (row = b * num_beams + beam).  One step is
  * kw_beam_logprobs then kw_beam_select; both read the device cur_len and do nothing once *done != 0,

@@ -97,7 +97,7 @@ __global__ __launch_bounds__(ST) void greedy_step_kernel(kw_sampler_args a) {
 // a serial walk over the row); each slice publishes its (max, first index, finished flag) write-through,
 // and the last of all B x NSPLIT workgroups to arrive combines every row's slices in slice order (first
 // index on ties, as torch.argmax) and finishes the step exactly as greedy_step_kernel does.
-constexpr int SPLIT_T = 512, NSPLIT = 8, SUNR = 16, PART = 8;  // PART: floats published per slice
+// (SPLIT_T, NSPLIT, SUNR, PART: processors.h, with the timestamp-mode slice statistics and merge kw_spec_accept shares)
 
 __global__ __launch_bounds__(SPLIT_T) void greedy_step_split_kernel(kw_sampler_args a) {
   __shared__ float shf[SPLIT_T / 64];
@@ -218,40 +218,6 @@ __global__ __launch_bounds__(SPLIT_T) void greedy_step_split_kernel(kw_sampler_a
 // maximum (+ first index), its own maximum with the sum of exp(s - that maximum), and the timestamp
 // sum of exp(s - timestamp maximum); the row's last arriver merges them (log-sum-exp rescaling), applies
 // the rule and picks the token (first index on ties, text before timestamps).
-__device__ __forceinline__ float blk_max(float v, float* sh) {
-  v = wave_max(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = sh[0];
-  for (int i = 1; i < SPLIT_T / 64; ++i) r = fmaxf(r, sh[i]);
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ float blk_sum(float v, float* sh) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = 0.f;
-  for (int i = 0; i < SPLIT_T / 64; ++i) r += sh[i];
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ void blk_argmax(float& best, int& bi, float* shf, int* shi) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float ob = __shfl_xor(best, o, 64);
-    const int oi = __shfl_xor(bi, o, 64);
-    if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
-  }
-  if ((threadIdx.x & 63) == 0) { shf[threadIdx.x >> 6] = best; shi[threadIdx.x >> 6] = bi; }
-  __syncthreads();
-  best = shf[0];
-  bi = shi[0];
-  for (int i = 1; i < SPLIT_T / 64; ++i)
-    if (shf[i] > best || (shf[i] == best && shi[i] < bi)) { best = shf[i]; bi = shi[i]; }
-  __syncthreads();
-}
-
 __global__ __launch_bounds__(SPLIT_T) void greedy_step_split_ts_kernel(kw_sampler_args a) {
   __shared__ float shf[SPLIT_T / 64];
   __shared__ int shi[SPLIT_T / 64];
@@ -266,14 +232,7 @@ __global__ __launch_bounds__(SPLIT_T) void greedy_step_split_ts_kernel(kw_sample
   const int v0 = sl * per, v1 = min(V, v0 + per);
   float xv[SUNR];
   bool mk[SUNR];
-#pragma unroll
-  for (int u = 0; u < SUNR; ++u) {  // the slice's logits and mask bytes in flight while the history is scanned
-    const int v = v0 + tid + u * SPLIT_T, vc = min(v, v1 - 1);  // unconditional (clamped) loads: no branches
-    const float xr = x[vc];                                           // and phis between them
-    const uint8_t mr = a.suppress_mask[vc];
-    xv[u] = v < v1 ? xr : -INFINITY;
-    mk[u] = v < v1 ? mr != 0 : true;
-  }
+  split_load(x, a.suppress_mask, v0, v1, xv, mk);  // in flight while the history is scanned
   // ---- row state from the id history (as kwp::row_state, 512 threads) ----
   int fin = 0, lsp = -1;
   for (int p = a.begin_index + tid; p < L; p += SPLIT_T) {
@@ -289,111 +248,22 @@ __global__ __launch_bounds__(SPLIT_T) void greedy_step_split_ts_kernel(kw_sample
   if (tid == 0) {
     int lp = shi[0];
     for (int i = 1; i < SPLIT_T / 64; ++i) lp = max(lp, shi[i]);
-    RowState st;
-    st.L = L; st.begin = a.begin_index; st.ts_begin = a.ts_begin; st.no_ts = a.no_ts_id; st.eos = a.eos_id;
-    st.rt = 1; st.max_init = a.max_initial_ts; st.ban_text = 0;
-    const int n = L - a.begin_index;
-    st.first_step = (L == a.begin_index);
-    st.last_ts = n >= 1 && ids[L - 1] >= a.ts_begin;
-    st.pen_ts = n < 2 || ids[L - 2] >= a.ts_begin;
-    st.has_stamp = lp >= 0;
-    st.stamp_lo = st.has_stamp ? ((st.last_ts && !st.pen_ts) ? (int)ids[lp] : (int)ids[lp] + 1) : 0;
-    st_sh = st;
+    st_sh = split_row_state(ids, L, lp, a.begin_index, a.ts_begin, a.no_ts_id, a.eos_id, 1, a.max_initial_ts);
   }
   __syncthreads();
   const RowState st = st_sh;
-  // ---- processed scores of the slice (held in registers) and their statistics ----
-  float sv[SUNR];
-  float mt = -INFINITY, ms = -INFINITY;
-  int it = 0x7fffffff, is = 0x7fffffff;
-#pragma unroll
-  for (int u = 0; u < SUNR; ++u) {
-    const int v = v0 + tid + u * SPLIT_T;
-    sv[u] = v < v1 ? process_m(st, mk[u], a.begin_suppress, a.n_begin_suppress, v, xv[u]) : -INFINITY;
-    if (v < v1) {
-      if (v < st.ts_begin) {
-        if (sv[u] > mt || (sv[u] == mt && v < it)) { mt = sv[u]; it = v; }
-      } else {
-        if (sv[u] > ms || (sv[u] == ms && v < is)) { ms = sv[u]; is = v; }
-      }
-    }
-  }
-  for (int vb = v0 + SPLIT_T * SUNR; vb < v1; vb += SPLIT_T) {  // V > NSPLIT * 8192 only
-    const int v = vb + tid;
-    if (v < v1) {
-      const float s = process(st, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, v, x[v]);
-      if (v < st.ts_begin) {
-        if (s > mt || (s == mt && v < it)) { mt = s; it = v; }
-      } else if (s > ms || (s == ms && v < is)) { ms = s; is = v; }
-    }
-  }
-  blk_argmax(mt, it, shf, shi);
-  blk_argmax(ms, is, shf, shi);
-  const float mall = fmaxf(mt, ms);
-  float sa = 0.f, sts = 0.f;
-  if (mall > -INFINITY) {
-#pragma unroll
-    for (int u = 0; u < SUNR; ++u) {
-      const int v = v0 + tid + u * SPLIT_T;
-      if (v < v1 && sv[u] > -INFINITY) {
-        sa += expf(sv[u] - mall);
-        if (v >= st.ts_begin) sts += expf(sv[u] - ms);
-      }
-    }
-    for (int vb = v0 + SPLIT_T * SUNR; vb < v1; vb += SPLIT_T) {
-      const int v = vb + tid;
-      if (v < v1) {
-        const float s = process(st, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, v, x[v]);
-        if (s > -INFINITY) {
-          sa += expf(s - mall);
-          if (v >= st.ts_begin) sts += expf(s - ms);
-        }
-      }
-    }
-  }
-  sa = blk_sum(sa, shf);
-  sts = blk_sum(sts, shf);
+  // ---- the slice's statistics over its processed scores, published; the row's last arriver merges ----
+  float vals[7];
+  split_slice_stats(st, x, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, v0, v1, xv, mk, shf, shi, vals);
   if (tid != 0) return;
   float* part = reinterpret_cast<float*>(a.workspace) + ((int64_t)b * NSPLIT + sl) * PART;
   int* rcnt = reinterpret_cast<int*>(a.workspace) + (int64_t)a.B * NSPLIT * PART + b;
-  const float vals[7] = {mt, __int_as_float(it), ms, __int_as_float(is), mall, sa, sts};
-#pragma unroll
-  for (int i = 0; i < 7; ++i) __hip_atomic_store(part + i, vals[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  split_publish(part, vals);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   const int prev = __hip_atomic_fetch_add(rcnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   if (prev != NSPLIT - 1) return;
   __hip_atomic_store(rcnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  const float* row = reinterpret_cast<const float*>(a.workspace) + (int64_t)b * NSPLIT * PART;
-  float P[NSPLIT][7];
-#pragma unroll
-  for (int q = 0; q < NSPLIT; ++q)  // every partial load in flight before the merge
-#pragma unroll
-    for (int i = 0; i < 7; ++i) P[q][i] = __hip_atomic_load(row + PART * q + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  float bt = -INFINITY, bs = -INFINITY, M = -INFINITY, Mts = -INFINITY;
-  int jt = 0x7fffffff, js = 0x7fffffff;
-  for (int q = 0; q < NSPLIT; ++q) {  // slice order = index order
-    const int qt = __float_as_int(P[q][1]), qs = __float_as_int(P[q][3]);
-    if (P[q][0] > bt || (P[q][0] == bt && qt < jt)) { bt = P[q][0]; jt = qt; }
-    if (P[q][2] > bs || (P[q][2] == bs && qs < js)) { bs = P[q][2]; js = qs; }
-    M = fmaxf(M, P[q][4]);
-  }
-  Mts = bs;
-  float S = 0.f, Sts = 0.f;
-  for (int q = 0; q < NSPLIT; ++q) {
-    if (P[q][4] > -INFINITY) S += P[q][5] * expf(P[q][4] - M);
-    if (P[q][2] > -INFINITY) Sts += P[q][6] * expf(P[q][2] - Mts);
-  }
-  int ban = 0;
-  if (M > -INFINITY) {
-    const float lse = logf(S);
-    const float lp_text_max = (bt - M) - lse;
-    const float lp_ts_max = (Mts - M) - lse;
-    const float ts_lse = lp_ts_max > -INFINITY ? lp_ts_max + logf(Sts) : -INFINITY;
-    ban = ts_lse > lp_text_max;
-  }
-  int ii;
-  if (ban) ii = js;
-  else ii = (bs > bt) ? js : jt;  // a tie keeps the text token (the lower index)
+  int ii = split_merge_token(reinterpret_cast<const float*>(a.workspace) + (int64_t)b * NSPLIT * PART, 1);
   if (ii == 0x7fffffff) ii = 0;
   const int64_t tok = fin ? (int64_t)a.pad_id : (int64_t)ii;
   a.ids[(int64_t)b * a.ids_stride + L] = tok;

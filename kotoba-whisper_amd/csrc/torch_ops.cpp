@@ -451,6 +451,57 @@ void sample_step(const Tensor& logits, const Tensor& suppress_mask, const option
   check(kw_sample_step(&a, stream_of(logits)), w);
 }
 
+// ---- speculative decoding: the accept step ----------------------------------------------------------------
+// cfg = [return_timestamps, ts_begin, no_ts_id, eos_id, pad_id, max_initial_ts, max_length, begin_index, K];
+// logits f32 [K + 1][V]; ids int64: the row (1-D, or row 0 of a 2-D tensor)
+void spec_accept(const Tensor& logits, const Tensor& suppress_mask, const optional<Tensor>& begin_suppress, Tensor& ids,
+                 Tensor& cur_len, Tensor& unfinished, Tensor& n_unfinished, optional<Tensor> asst_cur_len,
+                 optional<Tensor> asst_unfinished, optional<Tensor> verify_len, optional<Tensor> stats, Tensor& workspace,
+                 std::vector<int64_t> cfg) {
+  const char* w = "kw_spec_accept";
+  dev(logits, w), dev(suppress_mask, w), dev(begin_suppress, w), dev(ids, w), dev(cur_len, w), dev(unfinished, w);
+  dev(n_unfinished, w), dev(asst_cur_len, w), dev(asst_unfinished, w), dev(verify_len, w), dev(stats, w), dev(workspace, w);
+  TORCH_CHECK_VALUE(cfg.size() == 9, "kw_spec_accept: cfg must hold 9 integers");
+  const int64_t K = cfg[8];
+  TORCH_CHECK_VALUE(logits.dim() == 2 && logits.is_contiguous() && logits.scalar_type() == at::kFloat &&
+                        logits.size(0) == K + 1,
+                    "kw_spec_accept: logits must be a contiguous (K + 1, V) float32 tensor");
+  const int64_t V = logits.size(1);
+  auto i32 = [](const Tensor& t, int64_t n) { return t.scalar_type() == at::kInt && t.numel() >= n; };
+  TORCH_CHECK_VALUE(i32(cur_len, 1) && i32(unfinished, 1) && i32(n_unfinished, 1) &&
+                        (!asst_cur_len.has_value() || i32(*asst_cur_len, 1)) &&
+                        (!asst_unfinished.has_value() || i32(*asst_unfinished, 1)) &&
+                        (!verify_len.has_value() || i32(*verify_len, 1)) && (!stats.has_value() || i32(*stats, 3)),
+                    "kw_spec_accept: cur_len, unfinished, n_unfinished, asst_cur_len, asst_unfinished, verify_len int32 "
+                    "[1], stats int32 [3]");
+  TORCH_CHECK_VALUE(ids.scalar_type() == at::kLong && ids.stride(-1) == 1 && ids.size(-1) >= cfg[6] &&
+                        suppress_mask.scalar_type() == at::kByte && suppress_mask.numel() >= V,
+                    "kw_spec_accept: ids int64 [>= max_length], suppress_mask uint8 [V]");
+  kw_spec_accept_args a{};
+  a.logits = ptr<const float>(logits);
+  a.V = V, a.K = (int32_t)K;
+  a.suppress_mask = ptr<const uint8_t>(suppress_mask);
+  a.begin_suppress = optr<const int32_t>(begin_suppress);
+  a.n_begin_suppress = begin_suppress.has_value() ? (int32_t)begin_suppress->numel() : 0;
+  a.return_timestamps = (int32_t)cfg[0];
+  a.ts_begin = (int32_t)cfg[1], a.no_ts_id = (int32_t)cfg[2], a.eos_id = (int32_t)cfg[3], a.pad_id = (int32_t)cfg[4];
+  a.max_initial_ts = (int32_t)cfg[5];
+  a.ids = ptr<int64_t>(ids);
+  a.ids_stride = ids.size(-1);
+  a.cur_len = ptr<int32_t>(cur_len);
+  a.max_length = (int32_t)cfg[6], a.begin_index = (int32_t)cfg[7];
+  a.unfinished = ptr<int32_t>(unfinished);
+  a.n_unfinished = ptr<int32_t>(n_unfinished);
+  a.asst_cur_len = optr<int32_t>(asst_cur_len);
+  a.asst_unfinished = optr<int32_t>(asst_unfinished);
+  a.verify_len = optr<int32_t>(verify_len);
+  a.stats = optr<int32_t>(stats);
+  a.workspace = ptr(workspace);
+  a.ws_bytes = (size_t)workspace.numel() * workspace.element_size();
+  c10::DeviceGuard g(logits.device());
+  check(kw_spec_accept(&a, stream_of(logits)), w);
+}
+
 // ---- LM head + greedy step in one launch (no timestamps) ------------------------------------------------
 // lm_geo = [x_offset, ldx, M, N, K]; cfg = [eos_id, pad_id, max_length, begin_index]
 void dec_lm_greedy(const Tensor& x, const Tensor& W, const optional<Tensor>& bias, const Tensor& ln_colsum,
@@ -732,6 +783,7 @@ int64_t workspace_bytes(std::string kind, std::vector<int64_t> d) {
   if (kind == "cross_attn") return (int64_t)kw_cross_attn_workspace(n(0), n(1), n(2), n(3), n(4));
   if (kind == "greedy_step") return (int64_t)kw_greedy_step_workspace(n(0));
   if (kind == "sample_step") return (int64_t)kw_sample_step_workspace(n(0));
+  if (kind == "spec_accept") return (int64_t)kw_spec_accept_workspace(n(0));
   if (kind == "lm_greedy") return (int64_t)kw_dec_lm_greedy_workspace(n(0), n(1));
   if (kind == "qkv_self") return (int64_t)kw_dec_qkv_self_workspace(n(0), n(1));
   if (kind == "xq_cross") return (int64_t)kw_dec_xq_cross_workspace(n(0), n(1), n(2), n(3));
@@ -783,6 +835,9 @@ TORCH_LIBRARY(kw, m) {
         "Tensor(c!) unfinished, Tensor(d!) counter, Tensor(e!) n_unfinished, Tensor inv_temperature, Tensor seed, "
         "Tensor attempt, Tensor(f!) sum_logprob, Tensor(g!) n_tokens, Tensor? active, Tensor(h!)? noise_out, "
         "Tensor(i!) workspace, int[] cfg) -> ()");
+  m.def("spec_accept(Tensor logits, Tensor suppress_mask, Tensor? begin_suppress, Tensor(a!) ids, Tensor(b!) cur_len, "
+        "Tensor(c!) unfinished, Tensor(d!) n_unfinished, Tensor(e!)? asst_cur_len, Tensor(f!)? asst_unfinished, "
+        "Tensor(g!)? verify_len, Tensor(h!)? stats, Tensor(i!) workspace, int[] cfg) -> ()");
   m.def("dec_lm_greedy(Tensor x, Tensor W, Tensor? bias, Tensor ln_colsum, Tensor(a!)? logits, Tensor suppress_mask, "
         "Tensor? begin_suppress, Tensor(b!) ids, Tensor(c!) cur_len, Tensor(d!) unfinished, Tensor(e!) n_unfinished, "
         "Tensor(f!) workspace, int[] lm_geo, float ln_eps, int[] cfg) -> ()");
@@ -828,6 +883,7 @@ TORCH_LIBRARY_IMPL(kw, CUDA, m) {
   m.impl("dec_xq_cross_fp8", &dec_xq_cross_fp8);
   m.impl("greedy_step", &greedy_step);
   m.impl("sample_step", &sample_step);
+  m.impl("spec_accept", &spec_accept);
   m.impl("dec_lm_greedy", &dec_lm_greedy);
   m.impl("beam_logprobs", &beam_logprobs);
   m.impl("beam_logprobs_rep", &beam_logprobs_rep);

@@ -23,7 +23,7 @@ TORCH_OPS = ("log_mel", "mel_to_time_major", "gemm", "dec_linear", "pack_weight"
              "self_attn_step", "dec_qkv_self", "dec_xq_cross", "cross_attn_step", "greedy_step", "sample_step", "dec_lm_greedy",
              "beam_logprobs", "beam_select", "align_capture", "align_weights", "align_reduce", "dtw", "cross_kv_quant",
              "cross_attn_step_fp8", "dec_xq_cross_fp8", "self_attn_step_masked", "repeat_process", "beam_logprobs_rep",
-             "beam_select_parents", "align_weights_rows")
+             "beam_select_parents", "align_weights_rows", "spec_accept")
 
 KW_OK, KW_EINVAL, KW_EHIP, KW_EUNSUPPORTED = 0, 1, 2, 3
 KW_DT_F32, KW_DT_BF16 = 0, 1
@@ -115,6 +115,21 @@ class SampleArgs(ctypes.Structure):
     ]
 
 
+class SpecAcceptArgs(ctypes.Structure):
+    _fields_ = [
+        ("logits", c_vp), ("V", c_i64), ("K", c_i32),
+        ("suppress_mask", c_vp), ("begin_suppress", c_vp), ("n_begin_suppress", c_i32),
+        ("return_timestamps", c_i32),
+        ("ts_begin", c_i32), ("no_ts_id", c_i32), ("eos_id", c_i32), ("pad_id", c_i32),
+        ("max_initial_ts", c_i32),
+        ("ids", c_vp), ("ids_stride", c_i64),
+        ("cur_len", c_vp), ("max_length", c_i32), ("begin_index", c_i32),
+        ("unfinished", c_vp), ("n_unfinished", c_vp),
+        ("asst_cur_len", c_vp), ("asst_unfinished", c_vp), ("verify_len", c_vp), ("stats", c_vp),
+        ("workspace", c_vp), ("ws_bytes", ctypes.c_size_t),
+    ]
+
+
 class BeamLogprobsArgs(ctypes.Structure):
     _fields_ = [
         ("logits", c_vp), ("R", c_i64), ("V", c_i64),
@@ -180,6 +195,8 @@ EXPORTS = {
     "kw_greedy_step_workspace": (ctypes.c_size_t, [c_i64]),
     "kw_sample_step": (ctypes.c_int, [ctypes.POINTER(SampleArgs), c_vp]),
     "kw_sample_step_workspace": (ctypes.c_size_t, [c_i64]),
+    "kw_spec_accept": (ctypes.c_int, [ctypes.POINTER(SpecAcceptArgs), c_vp]),
+    "kw_spec_accept_workspace": (ctypes.c_size_t, [c_i64]),
     "kw_dec_lm_greedy": (ctypes.c_int, [ctypes.POINTER(DecLinearArgs), ctypes.POINTER(SamplerArgs), c_vp]),
     "kw_dec_lm_greedy_workspace": (ctypes.c_size_t, [c_i64, c_i64]),
     "kw_dec_lm_greedy_supported": (ctypes.c_int, [c_i64, c_i64, c_i64]),

@@ -265,8 +265,11 @@ class DecodeSession:
                                                         dtype=self.eng.dtype)
         return log
 
-    def _step_plans(self, q: int, fused: bool = False, align=None, begin_index: int = 0, masked: bool = False):
+    def _step_plans(self, q: int, fused: bool = False, align=None, begin_index: int = 0, masked: bool = False,
+                    all_rows: torch.Tensor | None = None):
         """The decoder forward for q new positions per row (q = prompt length for the prefill, 1 after).
+        ``all_rows`` (speculative decoding's verify forward): an f32 [R * q][V] buffer; the LM head then runs on every
+        one of the q positions into it instead of on the last one into ``self.logits``.  None: exactly the plain plan.
         ``align`` (q == 1): the alignment (layer, head) pairs whose cross-attention queries every step logs
         (kw_align_capture after the layer's query projection; such a layer takes the two-launch cross path, which
         leaves the query in global memory and is bitwise the fused block).  None: exactly the plain plan.
@@ -280,6 +283,10 @@ class DecodeSession:
             if align is not None:
                 raise NotImplementedError("token timestamps with a per-row key_start")
             key = (q, fused, "masked")
+        if all_rows is not None:
+            if align is not None or masked:
+                raise NotImplementedError("an all-rows LM head with token timestamps or a per-row key_start")
+            key = (q, fused, "all_rows", all_rows.data_ptr())
         self_kind = "self_masked" if masked else "self"
         if key in self._plans:
             return self._plans[key]
@@ -340,8 +347,12 @@ class DecodeSession:
                 seq.append(lin(b["ffn"], lay["fc2_w"], rows, d, s.decoder_ffn_dim, bias=lay["fc2_b"],
                                resid=(h, hb, d, 0), workspace=ws, tag="fc2", hb_tiled=tiled))
             # final LayerNorm (folded into the packed LM head) + proj_out on the last position of every row
-            seq.append(lin(hb, eng.lm_w, B, s.vocab_size, d, ldx=xld or q * d, x_offset=(q - 1) * d,
-                           ln=(eps, eng.lm_cs), bias=eng.lm_b, C=self.logits, workspace=ws, tag="lm_head"))
+            if all_rows is not None:  # (q > 1 here, so hb is row-major)
+                seq.append(lin(hb, eng.lm_w, rows, s.vocab_size, d, ldx=xld, ln=(eps, eng.lm_cs), bias=eng.lm_b,
+                               C=all_rows, workspace=ws, tag="lm_head"))
+            else:
+                seq.append(lin(hb, eng.lm_w, B, s.vocab_size, d, ldx=xld or q * d, x_offset=(q - 1) * d,
+                               ln=(eps, eng.lm_cs), bias=eng.lm_b, C=self.logits, workspace=ws, tag="lm_head"))
             self._plans[key] = seq
             return seq
         seq = [("embed", q, b["h"])]
@@ -364,13 +375,19 @@ class DecodeSession:
                               epilogue=L.KW_EPI_RESID)
         seq.append(("ln", b["h"], eng.dec_ln_g, eng.dec_ln_b, b["x"]))
         # LM head on the last position of every row (proj_out tied to embed_tokens, f32 logits)
-        seq += self._gemm(b["x"], eng.lm_w, self.logits, B, s.vocab_size, d, lda=q * d, a_offset=(q - 1) * d)
+        if all_rows is not None:
+            seq += self._gemm(b["x"], eng.lm_w, all_rows, rows, s.vocab_size, d)
+        else:
+            seq += self._gemm(b["x"], eng.lm_w, self.logits, B, s.vocab_size, d, lda=q * d, a_offset=(q - 1) * d)
         self._plans[key] = seq
         return seq
 
-    def _run(self, seq):
+    def _run(self, seq, cur_len: torch.Tensor | None = None):
+        """Launch ``seq``.  ``cur_len``: the device length its embedding and self-attention read instead of this
+        session's own (speculative decoding's verify forward runs ahead of ``self.cur_len``)."""
         eng, s = self.eng, self.eng.shape
         H, B = eng.H, self.R
+        cl = self.cur_len if cur_len is None else cur_len
         for p in seq:
             if not isinstance(p, tuple):
                 p()
@@ -379,15 +396,15 @@ class DecodeSession:
             if k == "ln":
                 ops.layernorm(p[1], p[2], p[3], s.layer_norm_eps, p[4])
             elif k == "embed":
-                ops.embed(self.ids, B, p[1], self.cur_len, eng.tok_emb, eng.dec_pos, p[2], p[3] if len(p) > 3 else None,
+                ops.embed(self.ids, B, p[1], cl, eng.tok_emb, eng.dec_pos, p[2], p[3] if len(p) > 3 else None,
                           hb_tiled=len(p) > 4 and p[4])
             elif k == "self":
                 _, q, qkv, li, out = p
-                ops.self_attn_step(qkv, B, q, H, _HD, self.kc[li], self.vc[li], T_MAX, self.cur_len, out, self.self_ws,
+                ops.self_attn_step(qkv, B, q, H, _HD, self.kc[li], self.vc[li], T_MAX, cl, out, self.self_ws,
                                    bp=self.bp if q == 1 else None)
             elif k == "self_masked":
                 _, q, qkv, li, out = p
-                ops.self_attn_step_masked(qkv, B, q, H, _HD, self.kc[li], self.vc[li], T_MAX, self.cur_len, self.key_start,
+                ops.self_attn_step_masked(qkv, B, q, H, _HD, self.kc[li], self.vc[li], T_MAX, cl, self.key_start,
                                           out, self.self_ws, bp=self.bp if q == 1 else None)
             elif k == "cross":  # rows b*nb*q + (beam*q + i) attend to item b's K/V
                 _, q, qx, li, out, ws = p

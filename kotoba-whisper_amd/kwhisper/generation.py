@@ -36,6 +36,21 @@ TF/models/whisper/generation_whisper.py:383-968):
                                               TF/generation/utils.py:1174-1183, TF/generation/logits_process.py:406-413, 1121-1139
     ``generate_multitask``, ``pseudo_label*`` and ``ASRPipeline(generate_kwargs=...)`` forward their keywords to
     ``generate`` unchanged, so the two reach it from there as well.
+  * ``assistant_model`` / ``num_assistant_tokens``: assisted (speculative) decoding at batch size 1 -- per seek pass
+    the assistant (another ``KWhisperForConditionalGeneration``) encodes the features with its own encoder and drafts
+    K tokens with its greedy step, this model checks them in one K + 1-position forward and ``kw_spec_accept``
+    (csrc/spec.hip) keeps the longest agreeing prefix plus the correction or bonus token (kwhisper/spec.py, one hipGraph
+    per round).  The tokens are this model's own greedy tokens with ``begin_suppress_tokens=None``, which the
+    reference drops with an assistant (:718-720); ``stats["assisted"]`` = rounds, drafted, accepted.
+                                              TF/generation/utils.py ``_assisted_decoding``, TF/generation/candidate_generator.py
+
+Deliberate differences of assisted generate from transformers 5.15.0:
+  * K is constant: from the call, else the assistant's ``generation_config.num_assistant_tokens``, else 5.  The
+    reference's default schedule changes K with the acceptance, which changes speed only, never tokens;
+  * the tokens are held to this engine's greedy ``generate()``, not to the reference's assisted output: on the tiny
+    synthetic fixtures (CPU) that path equals the reference's own greedy output only on some ``return_timestamps=False``
+    rows, raises ``IndexError`` past position 448 on others, and with ``return_timestamps=True`` returns sequences of
+    hundreds to thousands of tokens.
 
 Deliberate differences of the fallback from transformers 5.15.0:
   * ``no_speech_threshold`` without ``logprob_threshold`` raises ``ValueError`` (the reference dies on an unbound local);
@@ -74,7 +89,7 @@ _SUPPORTED = {
     "output_scores", "output_logits", "time_precision", "time_precision_features", "num_segment_frames",
     "synced_gpus", "force_unique_generate_call", "prefix_allowed_tokens_fn", "prompt_condition_type",
     "monitor_progress", "use_cache", "num_return_sequences", "length_penalty", "early_stopping",
-    "repetition_penalty", "no_repeat_ngram_size",
+    "repetition_penalty", "no_repeat_ngram_size", "assistant_model", "num_assistant_tokens",
 }
 
 
@@ -118,6 +133,7 @@ class KWhisperForConditionalGeneration:
         self.config = ModelConfig(engine.shape)
         self.generation_config = engine.generation_config
         self._sessions = {}
+        self._spec_sessions = {}  # id(assistant engine) -> the paired SpecDecodeSession
         self.stats = {}
         # True: generate() also keeps every seek pass's decoded ids in stats["pass_ids"] (validation: a fixture of the
         # engine's own multi-pass trajectory, tools/dump_hipmel.py)
@@ -216,6 +232,15 @@ class KWhisperForConditionalGeneration:
             self._sessions[key] = self.engine.new_session(B, beams=beams)
         return self._sessions[key]
 
+    def _spec_session(self, assistant):
+        """The paired session of assisted generate (kwhisper/spec.py) with ``assistant``'s engine, kept per assistant."""
+        from .spec import SpecDecodeSession
+
+        key = id(assistant.engine)
+        if key not in self._spec_sessions:
+            self._spec_sessions[key] = (SpecDecodeSession(self.engine, assistant.engine), assistant.engine)
+        return self._spec_sessions[key][0]
+
     def generate(self, input_features=None, generation_config=None, logits_processor=None, stopping_criteria=None,
                  return_timestamps=None, task=None, language=None, is_multilingual=None, attention_mask=None,
                  return_dict_in_generate=None, return_segments=False, **kwargs):
@@ -227,7 +252,7 @@ class KWhisperForConditionalGeneration:
             )
         if logits_processor or stopping_criteria:
             raise NotImplementedError("custom logits_processor / stopping_criteria are not supported on device")
-        for k in ("prefix_allowed_tokens_fn", "assistant_model", "output_scores"):
+        for k in ("prefix_allowed_tokens_fn", "output_scores"):
             if kwargs.get(k) is not None and kwargs.get(k) is not False:
                 raise NotImplementedError(f"`{k}` is not supported by the MI355X engine yet")
         if kwargs.get("num_return_sequences") not in (None, 1):
@@ -297,6 +322,13 @@ class KWhisperForConditionalGeneration:
             if kwargs.get("return_token_timestamps"):
                 raise NotImplementedError("`return_token_timestamps` is not supported with cross_kv_dtype='fp8_e4m3' "
                                           "(the alignment weights read the bf16 K cache); use the bf16 cache")
+        # assisted (speculative) generate: the assistant drafts, this model verifies -- its own greedy tokens
+        assistant = kwargs.get("assistant_model")
+        num_assist = 0
+        if assistant is not None:
+            num_assist = _assistant_arguments(self, assistant, kwargs, num_beams=num_beams, fallback=fallback,
+                                              prompted=prompted, repeat=repeat)
+            gen.begin_suppress_tokens = None  # dropped with an assistant (generation_whisper.py:718-720)
         length_penalty = kwargs.get("length_penalty", getattr(gen, "length_penalty", 1.0))
         early_stopping = kwargs.get("early_stopping", getattr(gen, "early_stopping", False))
         max_new_tokens = kwargs.get("max_new_tokens")
@@ -334,6 +366,13 @@ class KWhisperForConditionalGeneration:
                 if isinstance(enc_given, (tuple, list)) else enc_given
             B, total = eh.shape[0], eh.shape[1] * 2
             feats = None
+        if assistant is not None:
+            if B > 1:
+                raise ValueError("assisted generate is only supported for batch_size = 1")
+            if feats is None:
+                raise NotImplementedError("`assistant_model` with `encoder_outputs` is not supported by the MI355X "
+                                          "engine yet (the assistant encodes the features with its own encoder)")
+        assisted = {"rounds": 0, "drafted": 0, "accepted": 0}
         nseg = s.n_frames
         shortform = total <= nseg
         if prompted and fallback and shortform:
@@ -451,11 +490,21 @@ class KWhisperForConditionalGeneration:
                 eff_max = max_length
             else:
                 eff_max = P + max_new_tokens
-            sess = self._session(cur, num_beams)
-            sess.set_encoder_output(enc, key=enc_key)
+            if assistant is not None:
+                # the assistant encodes the pass's features with its own encoder; the paired session decodes the row
+                sess = self._spec_session(assistant)
+                sess.set_encoder_output(enc, assistant.engine.encode(seg_in))
+            else:
+                sess = self._session(cur, num_beams)
+                sess.set_encoder_output(enc, key=enc_key)
             skip = [False] * cur
             rep_kw = {} if repeat is None else {"repeat": repeat}  # (None: the session calls as they ever were)
-            if fallback:
+            if assistant is not None:
+                ids = sess.generate(torch.from_numpy(prompt), gen, K=num_assist, max_length=eff_max,
+                                    return_timestamps=return_timestamps)
+                for k in assisted:
+                    assisted[k] += int(sess.last_stats[k])
+            elif fallback:
                 sot = None
                 if passes == 0 and feats is not None and whole and self._sot_logits is not None \
                         and self._sot_logits.shape[0] == cur:
@@ -518,6 +567,8 @@ class KWhisperForConditionalGeneration:
             self.stats["alignment"] = align_log
         if fallback:
             self.stats["fallback"] = fallback_log
+        if assistant is not None:
+            self.stats["assisted"] = assisted
         if return_dict_in_generate and not return_timestamps:
             res = {"sequences": torch.from_numpy(last_ids).to(eng.device)}
             if token_ts:  # _stack_split_outputs: the single pass's timestamps, prompt positions included
@@ -676,6 +727,35 @@ class KWhisperForConditionalGeneration:
                 r.pop()
         arr = np.asarray(rows, dtype=np.int64)
         return np.broadcast_to(arr, (B, arr.shape[1])).copy()
+
+
+def _assistant_arguments(model, assistant, kwargs, *, num_beams, fallback, prompted, repeat) -> int:
+    """Check an ``assistant_model`` call and return K, the constant number of tokens drafted per round: from the call
+    (``num_assistant_tokens``), else the assistant's generation config, else 5."""
+    if not isinstance(assistant, KWhisperForConditionalGeneration):
+        raise NotImplementedError("`assistant_model` must be a KWhisperForConditionalGeneration (both decoders run on "
+                                  "the MI355X engine); other assistants are not supported")
+    for on, what in ((num_beams > 1, "`num_beams` > 1"),
+                     (fallback, "the decoding fallback (thresholds or a temperature above 0)"),
+                     (bool(kwargs.get("return_token_timestamps")), "`return_token_timestamps`"),
+                     (prompted, "`prompt_ids` / `condition_on_prev_tokens`"),
+                     (repeat is not None, "`repetition_penalty` / `no_repeat_ngram_size`"),
+                     (getattr(model.engine, "cross_kv_fp8", False) or getattr(assistant.engine, "cross_kv_fp8", False),
+                      "cross_kv_dtype='fp8_e4m3'")):
+        if on:
+            raise NotImplementedError(f"`assistant_model` together with {what} is not supported by the MI355X engine "
+                                      "yet")
+    if assistant.engine.shape.vocab_size != model.engine.shape.vocab_size:
+        raise ValueError("Make sure the main and assistant model use the same tokenizer: their vocabularies differ "
+                         f"({model.engine.shape.vocab_size} vs {assistant.engine.shape.vocab_size} tokens)")
+    K = kwargs.get("num_assistant_tokens")
+    if K is None:
+        K = getattr(assistant.generation_config, "num_assistant_tokens", None)
+    if K is None:
+        K = 5
+    if not isinstance(K, int) or isinstance(K, bool) or not 1 <= K <= 31:
+        raise ValueError(f"`num_assistant_tokens` has to be an integer in [1, 31], but is {K}")
+    return K
 
 
 def _repeat_arguments(kwargs, gen):

@@ -5,7 +5,7 @@ ops wrap the ABI"), which fills the C ABI's argument block and launches on torch
 the kernels are ordinary torch ops to the dispatcher, to ``torch.cuda.graph`` capture and to
 ``torch.compile`` (fake implementations are registered: every op mutates its outputs and returns nothing).
 Tensors are plumbing only (device memory + stream); all arithmetic happens in the HIP kernels of
-``libkwhisper.so``.  The plan classes (``GemmPlan``, ``DecLinearPlan``, ``SamplerPlan``, ``SamplePlan``, ``RepeatPlan``, ``BeamStepPlan``)
+``libkwhisper.so``.  The plan classes (``GemmPlan``, ``DecLinearPlan``, ``SamplerPlan``, ``SamplePlan``, ``SpecAcceptPlan``, ``RepeatPlan``, ``BeamStepPlan``)
 validate once and keep the op arguments, so decode steps replay without re-validation.
 
 ``set_backend("ctypes")`` routes the same calls through the ctypes binding of the C ABI instead (used by
@@ -72,7 +72,7 @@ def _ws_bytes(kind: str, *dims) -> int:
     fn = {"dec_linear": "kw_dec_linear_workspace_bytes", "packed_weight": "kw_packed_weight_bytes",
           "self_attn": "kw_self_attn_workspace", "cross_attn": "kw_cross_attn_workspace",
           "greedy_step": "kw_greedy_step_workspace", "sample_step": "kw_sample_step_workspace", "beam_logprobs": "kw_beam_logprobs_workspace",
-          "lm_greedy": "kw_dec_lm_greedy_workspace", "dtw": "kw_dtw_workspace",
+          "lm_greedy": "kw_dec_lm_greedy_workspace", "dtw": "kw_dtw_workspace", "spec_accept": "kw_spec_accept_workspace",
           "qkv_self": "kw_dec_qkv_self_workspace", "xq_cross": "kw_dec_xq_cross_workspace",
           "qkv_self_status": "kw_dec_qkv_self_status_offset", "xq_cross_status": "kw_dec_xq_cross_status_offset",
           "cross_attn_status": "kw_cross_attn_status_offset"}[kind]
@@ -701,6 +701,75 @@ class SamplePlan:
             _kw().sample_step(*self._targs)
         else:
             L.check(_lib().kw_sample_step(self._ref, _s()), "kw_sample_step")
+
+
+SPEC_K_MAX = 31  # kw_spec_accept: K + 1 <= 32 positions per launch
+
+
+def spec_accept_workspace_bytes(K: int) -> int:
+    return _ws_bytes("spec_accept", K)
+
+
+class SpecAcceptPlan:
+    """Pre-built ``kw_spec_accept`` call: the accept step of one speculative-decoding round, for one row.  ``logits``:
+    f32 [K + 1][V], the main decoder's logits of positions L .. L + K (L = ``*cur_len``); ``ids``: the row (int64, 1-D
+    or row 0 of a 2-D tensor) with the K drafts at [L, L + K).  Every position's token is ``SamplerPlan``'s at that
+    length; the longest agreeing prefix is kept, then the correction or the bonus token.  Writes ``cur_len``,
+    ``unfinished``, ``n_unfinished`` and, where given, ``asst_cur_len`` (= the new length), ``asst_unfinished`` (= 1),
+    ``verify_len`` (= the new length + K) and ``stats`` (int32 [3]: rounds, drafted, accepted -- added to).
+    ``workspace`` zero-filled (spec_accept_workspace_bytes); every launch leaves it zeroed."""
+
+    def __init__(self, logits, suppress_mask, begin_suppress, ids, cur_len, unfinished, n_unfinished, *, K,
+                 return_timestamps, ts_begin, no_ts_id, eos_id, pad_id, max_initial_ts, max_length, begin_index, workspace,
+                 asst_cur_len=None, asst_unfinished=None, verify_len=None, stats=None):
+        ts = (logits, suppress_mask, begin_suppress, ids, cur_len, unfinished, n_unfinished, asst_cur_len, asst_unfinished,
+              verify_len, stats, workspace)
+        _cuda(*ts)
+        K = int(K)
+        if not 1 <= K <= SPEC_K_MAX:
+            raise ValueError(f"kw_spec_accept: K must be in [1, {SPEC_K_MAX}]")
+        if logits.dim() != 2 or logits.dtype != torch.float32 or not logits.is_contiguous() or logits.shape[0] != K + 1:
+            raise ValueError("kw_spec_accept: logits must be a contiguous (K + 1, V) float32 tensor")
+        V = logits.shape[1]
+        for t, n in ((cur_len, 1), (unfinished, 1), (n_unfinished, 1), (asst_cur_len, 1), (asst_unfinished, 1),
+                     (verify_len, 1), (stats, 3)):
+            if t is not None and (t.dtype != torch.int32 or t.numel() < n):
+                raise ValueError("kw_spec_accept: cur_len, unfinished, n_unfinished, asst_cur_len, asst_unfinished, "
+                                 "verify_len int32 [1], stats int32 [3]")
+        if (ids.dtype != torch.int64 or ids.stride(-1) != 1 or ids.shape[-1] < max_length
+                or suppress_mask.dtype != torch.uint8 or suppress_mask.numel() < V):
+            raise ValueError("kw_spec_accept: ids int64 [>= max_length], suppress_mask uint8 [V]")
+        if workspace.numel() * workspace.element_size() < spec_accept_workspace_bytes(K):
+            raise ValueError("kw_spec_accept workspace too small")
+        self._keep = ts
+        mit = -1 if max_initial_ts is None else max_initial_ts
+        cfg = [int(bool(return_timestamps)), ts_begin, no_ts_id, eos_id, pad_id, mit, max_length, begin_index, K]
+        self._targs = (logits, suppress_mask, begin_suppress, ids, cur_len, unfinished, n_unfinished, asst_cur_len,
+                       asst_unfinished, verify_len, stats, workspace, cfg)
+        a = L.SpecAcceptArgs()
+        a.logits, a.V, a.K = logits.data_ptr(), V, K
+        a.suppress_mask = suppress_mask.data_ptr()
+        a.begin_suppress = begin_suppress.data_ptr() if begin_suppress is not None else None
+        a.n_begin_suppress = begin_suppress.numel() if begin_suppress is not None else 0
+        a.return_timestamps = int(bool(return_timestamps))
+        a.ts_begin, a.no_ts_id, a.eos_id, a.pad_id = ts_begin, no_ts_id, eos_id, pad_id
+        a.max_initial_ts = mit
+        a.ids, a.ids_stride, a.cur_len = ids.data_ptr(), ids.shape[-1], cur_len.data_ptr()
+        a.max_length, a.begin_index = max_length, begin_index
+        a.unfinished, a.n_unfinished = unfinished.data_ptr(), n_unfinished.data_ptr()
+        a.asst_cur_len = asst_cur_len.data_ptr() if asst_cur_len is not None else None
+        a.asst_unfinished = asst_unfinished.data_ptr() if asst_unfinished is not None else None
+        a.verify_len = verify_len.data_ptr() if verify_len is not None else None
+        a.stats = stats.data_ptr() if stats is not None else None
+        a.workspace, a.ws_bytes = workspace.data_ptr(), workspace.numel() * workspace.element_size()
+        self.args = a
+        self._ref = ctypes.byref(a)
+
+    def __call__(self):
+        if _BACKEND == "torch":
+            _kw().spec_accept(*self._targs)
+        else:
+            L.check(_lib().kw_spec_accept(self._ref, _s()), "kw_spec_accept")
 
 
 def lm_greedy_workspace_bytes(B: int, V: int) -> int:
