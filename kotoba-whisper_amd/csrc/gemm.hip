@@ -642,7 +642,15 @@ bool use256(const kw_gemm_args* a) {
   const bool aligned = a->ldc % vec == 0 && a->c_batch_stride % vec == 0 &&
                        (a->hs_head_dim <= 0 || a->hs_head_dim % vec == 0) && ((uintptr_t)a->C % 16) == 0 &&
                        ((uintptr_t)a->row_add % 16) == 0;
-  return aligned && a->N % PB == 0 && a->M >= 4 * PB;
+  // gemm256_kernel keeps its staging offsets (set_tile's soff) as 32-bit byte offsets from A and W: the last
+  // byte a row of either operand reaches must lie below 4 GiB (the 128x128 kernel carries 64-bit pointers)
+  const int64_t rpb = a->a_rows_per_batch > 0 ? a->a_rows_per_batch : a->M;
+  const int64_t lb = (a->M - 1) / rpb;  // last batch: its last row, and the last row of a whole batch before it
+  int64_t a_last = lb * a->a_batch_stride + (a->M - 1 - lb * rpb) * a->lda;
+  if (lb > 0) a_last = std::max(a_last, (lb - 1) * a->a_batch_stride + (rpb - 1) * a->lda);
+  const bool off32 = a->lda >= 0 && a->a_batch_stride >= 0 && (a_last + a->K) * 2 <= (int64_t)UINT32_MAX &&
+                     a->N * a->K * 2 <= (int64_t)UINT32_MAX;
+  return aligned && off32 && a->N % PB == 0 && a->M >= 4 * PB;
 }
 
 template <typename TC>
