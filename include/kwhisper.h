@@ -700,6 +700,42 @@ int kw_repeat_process(float* scores, int64_t R, int64_t V, const int64_t* ids, i
  * floats of the row's workspace record, and the split launch reads them -- kernel order, no in-launch hand-off. */
 int kw_beam_logprobs_rep(const kw_beam_logprobs_args* args, float penalty, int32_t ngram, kw_stream_t stream);
 
+/* ---- distillation loss on the teacher's logits (additive, ABI 112 unchanged) --------------------------
+ * The temperature KL of kotoba-whisper's train_step (run_distillation.py:614-622, 652-657): with
+ * p = softmax(teacher / T) and q = softmax(student / T) over the V columns of a row,
+ *   row_kl[r] = sum_v p_v (log p_v - log q_v)     (a term with p_v == 0 is 0, as KLDivLoss's xlogy makes it)
+ *   loss      = T^2 * sum_r row_kl[r] / n_valid   (n_valid = rows with labels[r] >= 0, counted on the device: the
+ *                                                  host never synchronises)
+ *   grad[r][v] = T * (q_v - p_v) / n_valid        (d loss / d student, in the student's dtype; NULL: forward only)
+ * A row with a negative label is ignored: exactly 0 in row_kl and in every element of its grad row.  n_valid == 0
+ * gives loss = NaN (the reference's 0 / 0) and an all-zero grad.
+ * teacher: f32 [N][ldt]; student: f32 or bf16 (s_dtype) [N][lds]; labels: int64 [N]; row_kl: f32 [N]; loss: f32 [1];
+ * grad: s_dtype [N][ldg].  Row strides are in elements and >= V; rows need element alignment only (V = 51865 with
+ * ld == V is fine, nothing is padded).  grad sharing a byte with student or teacher is KW_EINVAL (the reference's
+ * cross-entropy term still reads the student's logits).  Each logit is read twice (an online max / sum pass, then the
+ * terms), all accumulation is f32, and there are no float atomics: loss, row_kl and grad are bitwise the same from run
+ * to run.  workspace: >= kw_kd_loss_workspace(N) bytes, zero-filled before first use (calls leave it zeroed); three
+ * launches on `stream`.  Invalid arguments: KW_EINVAL with a message, nothing is launched. */
+typedef struct {
+  const float* teacher;
+  int64_t ldt;
+  const void* student;
+  int64_t lds;
+  int s_dtype;               /* KW_DT_F32 or KW_DT_BF16: student and grad */
+  const int64_t* labels;
+  int64_t N, V;
+  float temperature;         /* finite, > 0 */
+  float* row_kl;
+  float* loss;
+  void* grad;                /* or NULL */
+  int64_t ldg;
+  void* workspace;
+  size_t ws_bytes;
+} kw_kd_loss_args;
+
+int kw_kd_loss(const kw_kd_loss_args* args, kw_stream_t stream);
+size_t kw_kd_loss_workspace(int64_t N);
+
 #ifdef __cplusplus
 }
 #endif

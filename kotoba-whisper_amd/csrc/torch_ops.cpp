@@ -616,6 +616,41 @@ void repeat_process(Tensor& scores, const Tensor& ids, const Tensor& cur_len, do
         w);
 }
 
+// ---- distillation loss: temperature KL of teacher / student logits, forward + student gradient ------------
+void kd_loss(const Tensor& teacher, const Tensor& student, const Tensor& labels, double temperature, Tensor& row_kl,
+             Tensor& loss, optional<Tensor> grad, Tensor& workspace) {
+  const char* w = "kw_kd_loss";
+  dev(teacher, w), dev(student, w), dev(labels, w), dev(row_kl, w), dev(loss, w), dev(grad, w), dev(workspace, w);
+  TORCH_CHECK_VALUE(teacher.dim() == 2 && teacher.scalar_type() == at::kFloat && teacher.stride(1) == 1,
+                    "kw_kd_loss: teacher must be an (N, V) float32 tensor with unit inner stride");
+  const int64_t N = teacher.size(0), V = teacher.size(1);
+  TORCH_CHECK_VALUE(student.dim() == 2 && student.size(0) == N && student.size(1) == V && student.stride(1) == 1,
+                    "kw_kd_loss: student must be an (N, V) tensor like teacher, with unit inner stride");
+  const int sdt = dt_of(student);
+  TORCH_CHECK_VALUE(labels.dim() == 1 && labels.size(0) == N && labels.scalar_type() == at::kLong &&
+                        labels.is_contiguous(),
+                    "kw_kd_loss: labels must be a contiguous int64 [N] tensor");
+  TORCH_CHECK_VALUE(row_kl.scalar_type() == at::kFloat && row_kl.is_contiguous() && row_kl.numel() == N &&
+                        loss.scalar_type() == at::kFloat && loss.numel() == 1,
+                    "kw_kd_loss: row_kl float32 [N], loss float32 [1]");
+  if (grad.has_value())
+    TORCH_CHECK_VALUE(grad->dim() == 2 && grad->size(0) == N && grad->size(1) == V && grad->stride(1) == 1 &&
+                          grad->scalar_type() == student.scalar_type(),
+                      "kw_kd_loss: grad must be an (N, V) tensor of the student's dtype with unit inner stride");
+  // (a one-row tensor's stride(0) is arbitrary: V serves)
+  auto ld = [&](const Tensor& t) { return N == 1 ? V : t.stride(0); };
+  kw_kd_loss_args a{};
+  a.teacher = ptr<const float>(teacher), a.ldt = ld(teacher);
+  a.student = ptr(student), a.lds = ld(student), a.s_dtype = sdt;
+  a.labels = ptr<const int64_t>(labels);
+  a.N = N, a.V = V, a.temperature = (float)temperature;
+  a.row_kl = ptr<float>(row_kl), a.loss = ptr<float>(loss);
+  a.grad = optr(grad), a.ldg = grad.has_value() ? ld(*grad) : 0;
+  a.workspace = ptr(workspace), a.ws_bytes = (size_t)workspace.numel() * workspace.element_size();
+  c10::DeviceGuard g(teacher.device());
+  check(kw_kd_loss(&a, stream_of(teacher)), w);
+}
+
 // cfg = [B, num_beams, V, begin_index, max_length, eos_id, fill_id, early_stopping]; parent_log / fin_parent: both
 // (kw_beam_select_parents) or neither (kw_beam_select)
 void beam_select_impl(const char* w, const Tensor& cand_val, const Tensor& cand_idx, Tensor& ids, optional<Tensor> bp,
@@ -788,6 +823,7 @@ int64_t workspace_bytes(std::string kind, std::vector<int64_t> d) {
   if (kind == "qkv_self") return (int64_t)kw_dec_qkv_self_workspace(n(0), n(1));
   if (kind == "xq_cross") return (int64_t)kw_dec_xq_cross_workspace(n(0), n(1), n(2), n(3));
   if (kind == "beam_logprobs") return (int64_t)kw_beam_logprobs_workspace(n(0));
+  if (kind == "kd_loss") return (int64_t)kw_kd_loss_workspace(n(0));
   if (kind == "dtw") return (int64_t)kw_dtw_workspace(n(0), n(1), n(2));
   // byte offsets of the hand-off status words inside those workspaces (include/kwhisper.h)
   if (kind == "qkv_self_status") return (int64_t)kw_dec_qkv_self_status_offset(n(0), n(1));
@@ -862,6 +898,8 @@ TORCH_LIBRARY(kw, m) {
   m.def("align_reduce(Tensor weights, int A, int B, int T, int S, Tensor? frames, int filter_width, Tensor(a!) out, "
         "int a_total, int first, int last) -> ()");
   m.def("dtw(Tensor matrix, Tensor? frames, Tensor(a!) out, Tensor(b!) workspace) -> ()");
+  m.def("kd_loss(Tensor teacher, Tensor student, Tensor labels, float temperature, Tensor(a!) row_kl, Tensor(b!) loss, "
+        "Tensor(c!)? grad, Tensor(d!) workspace) -> ()");
 }
 
 TORCH_LIBRARY_IMPL(kw, CUDA, m) {
@@ -895,4 +933,5 @@ TORCH_LIBRARY_IMPL(kw, CUDA, m) {
   m.impl("align_weights", &align_weights);
   m.impl("align_reduce", &align_reduce);
   m.impl("dtw", &dtw);
+  m.impl("kd_loss", &kd_loss);
 }

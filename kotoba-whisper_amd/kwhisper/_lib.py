@@ -23,7 +23,7 @@ TORCH_OPS = ("log_mel", "mel_to_time_major", "gemm", "dec_linear", "pack_weight"
              "self_attn_step", "dec_qkv_self", "dec_xq_cross", "cross_attn_step", "greedy_step", "sample_step", "dec_lm_greedy",
              "beam_logprobs", "beam_select", "align_capture", "align_weights", "align_reduce", "dtw", "cross_kv_quant",
              "cross_attn_step_fp8", "dec_xq_cross_fp8", "self_attn_step_masked", "repeat_process", "beam_logprobs_rep",
-             "beam_select_parents", "align_weights_rows", "spec_accept")
+             "beam_select_parents", "align_weights_rows", "spec_accept", "kd_loss")
 
 KW_OK, KW_EINVAL, KW_EHIP, KW_EUNSUPPORTED = 0, 1, 2, 3
 KW_DT_F32, KW_DT_BF16 = 0, 1
@@ -130,6 +130,15 @@ class SpecAcceptArgs(ctypes.Structure):
     ]
 
 
+class KdLossArgs(ctypes.Structure):
+    _fields_ = [
+        ("teacher", c_vp), ("ldt", c_i64), ("student", c_vp), ("lds", c_i64), ("s_dtype", ctypes.c_int),
+        ("labels", c_vp), ("N", c_i64), ("V", c_i64), ("temperature", ctypes.c_float),
+        ("row_kl", c_vp), ("loss", c_vp), ("grad", c_vp), ("ldg", c_i64),
+        ("workspace", c_vp), ("ws_bytes", ctypes.c_size_t),
+    ]
+
+
 class BeamLogprobsArgs(ctypes.Structure):
     _fields_ = [
         ("logits", c_vp), ("R", c_i64), ("V", c_i64),
@@ -216,6 +225,8 @@ EXPORTS = {
     "kw_beam_select_parents": (ctypes.c_int, [ctypes.POINTER(BeamSelectArgs), c_vp, c_vp, c_vp]),
     "kw_align_weights_rows": (ctypes.c_int, [ctypes.c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64,
                                              ctypes.POINTER(c_i32), c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp]),
+    "kw_kd_loss": (ctypes.c_int, [ctypes.POINTER(KdLossArgs), c_vp]),
+    "kw_kd_loss_workspace": (ctypes.c_size_t, [c_i64]),
 }
 
 _lib = None

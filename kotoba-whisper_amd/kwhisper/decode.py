@@ -491,6 +491,107 @@ class DecodeSession:
             out.append(self.logits.clone())
         return torch.stack(out, 1)
 
+    # ------------------------------------------------------------------------------------------
+    # the many-row pass: logits of every position of a teacher-forced sequence (model.forward)
+    # ------------------------------------------------------------------------------------------
+    # bf16 engine: rows (R * T) from which forward_all takes the wide plan (kw_layernorm + kw_gemm over row-major
+    # weights) instead of the packed row-chunk plan, whose 32-row chunks stream the weights once per chunk.
+    # profiles/distill_forward.txt (large-v3, tools/distill_measure.py), decoder pass in ms, wide / chunk: 64 rows
+    # 11.4 / 6.9, 128 rows 12.96 / 12.67, 256 rows 13.5 / 14.7, 1024 rows 14.1 / 27.6, 4096 rows 27.6 / 81.9.  The
+    # chunk plan wins up to 128 rows, the wide plan from 256 on; nothing was measured in between, so the threshold is
+    # the first size at which the wide plan was seen to win.
+    WIDE_MIN_ROWS = 256
+
+    def _wide_plans(self, q: int):
+        """bf16 engine: the decoder body for q positions per row on whole-matrix kernels -- per linear a kw_layernorm
+        (f32 residual in, bf16 out; gamma / beta are folded into the weights, so it only normalises) and a kw_gemm
+        over the row-major weight (q-scale, GELU and the residual add into the f32 stream are its epilogues), the MFMA
+        tile prefill self-attention (kw_self_attn_step_masked with this session's all-zero key_start) and the
+        cross-attention step.  Ends with the final LayerNorm into the ``x`` buffer; the LM head is the caller's."""
+        key = (q, "wide")
+        if key in self._plans:
+            return self._plans[key]
+        eng, s = self.eng, self.eng.shape
+        w = eng.wide_weights()
+        b = self._buffers(q)
+        d, f, rows = s.d_model, s.decoder_ffn_dim, self.R * q
+        scale = _HD ** -0.5
+        h, x = b["h"], b["x"]
+        ln = ("ln", h, w["ln_one"], w["ln_zero"], x)
+        gemm, resid = ops.GemmPlan, dict(epilogue=L.KW_EPI_RESID)
+        seq = [("embed", q, h)]
+        for li, (lay, wl) in enumerate(zip(eng.dec_layers, w["layers"])):
+            seq += [ln, gemm(x, wl["qkv_w"], b["qkv"], rows, 3 * d, d, bias=lay["qkv_b"], scale=scale, scale_cols=d),
+                    ("self_masked", q, b["qkv"], li, b["attn"]),
+                    gemm(b["attn"], wl["o_w"], h, rows, d, d, bias=lay["o_b"], **resid),
+                    ln, gemm(x, wl["xq_w"], b["qx"], rows, d, d, bias=lay["xq_b"], scale=scale, scale_cols=d),
+                    ("cross", q, b["qx"], li, b["attn"], b["ws"]),
+                    gemm(b["attn"], wl["xo_w"], h, rows, d, d, bias=lay["xo_b"], **resid),
+                    ln, gemm(x, wl["fc1_w"], b["ffn"], rows, f, d, bias=lay["fc1_b"], gelu=True),
+                    gemm(b["ffn"], wl["fc2_w"], h, rows, d, f, bias=lay["fc2_b"], **resid)]
+        seq.append(ln)
+        self._plans[key] = seq
+        return seq
+
+    def _prefill_body(self, q: int):
+        """The prefill plan of q positions without its LM head (which reads the last position of every row only):
+        everything up to the final residual stream -- on the f32 engine up to the final LayerNorm into ``x``.  The
+        head is the plan's last entry; that is checked, not assumed."""
+        seq = self._step_plans(q)
+        head = seq[-1]
+        is_head = getattr(head, "tag", None) == "lm_head" if self.eng.packed else \
+            isinstance(head, ops.GemmPlan) and head._keep[2] is self.logits
+        if not is_head:
+            raise RuntimeError("the prefill plan no longer ends with its LM head")
+        return seq[:-1]
+
+    def forward_all(self, ids: torch.Tensor, plan: str | None = None) -> torch.Tensor:
+        """Raw f32 logits [R][T][V] of every position of the teacher-forced rows ``ids`` [R][T] (T <= 448), against
+        the cross K/V this session holds: the decoder of ``WhisperForConditionalGeneration.forward``
+        (TF modeling_whisper.py:690-795, proj_out :1080), no cache kept for a later step.
+
+        f32 engine: the prefill plan (kw_layernorm + kw_gemm) with the LM head on every row.  bf16 engine, ``plan``:
+        "chunk" = the packed prefill plan (kw_dec_linear in 32-row chunks), "wide" = ``_wide_plans``; None picks by
+        the row count (``WIDE_MIN_ROWS``).  The result is a new tensor every call (of the wide plan: a view of rows
+        padded to a multiple of 128 columns); everything else lives in this session's buffers.  Synchronises once, to
+        read the in-launch hand-off status words (``check_handoffs``)."""
+        eng, s = self.eng, self.eng.shape
+        if self.fp8:
+            raise NotImplementedError("forward_all over the fp8 cross K/V cache (there is no many-row fp8 "
+                                      "cross-attention kernel)")
+        if self.nb != 1:
+            raise NotImplementedError("forward_all on a beam session")
+        if ids.dim() != 2 or ids.shape[0] != self.R or not 1 <= ids.shape[1] <= T_MAX:
+            raise ValueError(f"forward_all: ids must be [{self.R}][1 .. {T_MAX}]")
+        if plan not in (None, "wide", "chunk") or (plan == "wide" and not eng.packed):
+            raise ValueError("forward_all: plan is None, 'chunk' or (bf16 engine) 'wide'")
+        R, T = ids.shape
+        d, V, rows = s.d_model, s.vocab_size, R * T
+        wide = eng.packed and (plan == "wide" or (plan is None and rows >= self.WIDE_MIN_ROWS))
+        self.forward_plan_last = "wide" if wide else ("chunk" if eng.packed else "f32")
+        self._keep_prefill(T)
+        self.ids[:, :T].copy_(ids.to(device=eng.device, dtype=torch.int64))
+        self.cur_len.fill_(T)
+        if wide:
+            w = eng.wide_weights()
+            out = torch.empty((rows, w["vpad"]), device=eng.device, dtype=torch.float32)
+            self._run(self._wide_plans(T))
+            ops.GemmPlan(self._buffers(T)["x"], w["lm_w"], out, rows, w["vpad"], d, bias=w["lm_b"])()
+        elif T == 1:  # (the q = 1 step plan keeps its activations fragment-major: its own LM head serves)
+            self._run(self._step_plans(1))
+            out = self.logits.clone()
+        else:
+            out = torch.empty((rows, V), device=eng.device, dtype=torch.float32)
+            self._run(self._prefill_body(T))
+            b = self._buffers(T)
+            if eng.packed:
+                ops.DecLinearPlan(b["hb"], eng.lm_w, rows, V, d, ln=(s.layer_norm_eps, eng.lm_cs), bias=eng.lm_b, C=out,
+                                  workspace=self.lin_ws, tag="lm_head")()
+            else:
+                ops.GemmPlan(b["x"], eng.lm_w, out, rows, V, d)()
+        self.check_handoffs()
+        return out.view(R, T, -1)[:, :, :V]
+
     def _pinned_slots(self, n: int) -> torch.Tensor:
         if self._pinned is None or self._pinned.numel() < n:
             self._pinned = torch.zeros((n,), dtype=torch.int32).pin_memory()

@@ -125,6 +125,7 @@ class WhisperEngine:
         self._enc_split = {}
         self._enc_streams = []
         self._kv_stage = {}  # fp8 cross K/V: the bf16 staging buffer of one layer group, per batch size
+        self._wide = []  # wide_weights(): the row-major decoder weights of forward(), made on first use
 
     # ------------------------------------------------------------------------------------------
     def _dev(self, t: torch.Tensor, dtype=None) -> torch.Tensor:
@@ -375,6 +376,36 @@ class WhisperEngine:
             out = torch.empty((2 * s.decoder_layers, B, self.H, T, _HD), device=self.device, dtype=self.dtype)
         ops.GemmPlan(enc, self.cross_kv_w, out, B * T, n, d, bias=self.cross_kv_b, epilogue=L.KW_EPI_HEADSPLIT,
                      hs_seq=T, hs_heads=self.H, hs_head_dim=_HD)()
+        return out
+
+    # ------------------------------------------------------------------------------------------
+    # the many-row decoder pass (DecodeSession.forward_all): row-major bf16 weights for kw_gemm
+    # ------------------------------------------------------------------------------------------
+    LM_PAD = 128  # kw_gemm (bf16) takes N % 128 == 0: the LM head's rows beyond the vocabulary are zero
+
+    def wide_weights(self) -> dict:
+        """bf16 engine: row-major copies of the decoder's packed weights -- the LayerNorm-folded values the decode
+        step multiplies, unpacked by an index permutation -- made on first use and shared by every lane: about
+        1.6 GB at large-v3 (32 layers x 46 MB + the 133 MB LM head).  An engine that never runs
+        ``forward()`` never makes them.  With gamma / beta folded into the weights the LayerNorm in front of such a
+        linear only normalises: ``ln_one`` / ``ln_zero`` are its gamma and beta."""
+        if self._wide:
+            return self._wide[0]
+        if not self.packed:
+            raise ValueError("wide_weights: the f32 engine's weights are row-major already")
+        s = self.shape
+        d, f, V = s.d_model, s.decoder_ffn_dim, s.vocab_size
+        un = ops.unpack_weight
+        layers = [dict(qkv_w=un(l["qkv_w"], 3 * d, d), o_w=un(l["o_w"], d, d), xq_w=un(l["xq_w"], d, d),
+                       xo_w=un(l["xo_w"], d, d), fc1_w=un(l["fc1_w"], f, d), fc2_w=un(l["fc2_w"], d, f))
+                  for l in self.dec_layers]
+        vpad = -(-V // self.LM_PAD) * self.LM_PAD
+        lm_b = torch.zeros((vpad,), device=self.device, dtype=torch.float32)
+        lm_b[:V] = self.lm_b
+        out = dict(layers=layers, lm_w=un(self.lm_w, V, d, rows=vpad), lm_b=lm_b, vpad=vpad,
+                   ln_one=torch.ones((d,), device=self.device, dtype=torch.float32),
+                   ln_zero=torch.zeros((d,), device=self.device, dtype=torch.float32))
+        self._wide.append(out)  # (lane() copies the reference to this list: lanes made before or after share one set)
         return out
 
     def lane(self) -> "WhisperEngine":

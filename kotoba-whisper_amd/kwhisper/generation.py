@@ -113,6 +113,59 @@ class EncoderOutput:
         raise IndexError(i)
 
 
+def shift_tokens_right(input_ids: torch.Tensor, pad_token_id: int, decoder_start_token_id: int) -> torch.Tensor:
+    """Labels -> decoder input ids (TF modeling_whisper.py ``shift_tokens_right``): one step to the right behind
+    ``decoder_start_token_id``, every -100 replaced by ``pad_token_id``."""
+    if pad_token_id is None:
+        raise ValueError("self.model.config.pad_token_id has to be defined.")
+    shifted = input_ids.new_zeros(input_ids.shape)
+    shifted[:, 1:] = input_ids[:, :-1]
+    shifted[:, 0] = decoder_start_token_id
+    shifted.masked_fill_(shifted == -100, pad_token_id)
+    return shifted
+
+
+class ForwardOutput:
+    """What ``forward()`` returns, read as HF's ``Seq2SeqLMOutput``: attributes, string keys, and the tuple of the
+    fields that are not None -- ``out[0]`` is the loss when there were labels, otherwise the logits."""
+
+    def __init__(self, logits, encoder_last_hidden_state, labels=None):
+        self.logits = logits
+        self.encoder_last_hidden_state = encoder_last_hidden_state
+        self._labels = labels
+        self._loss = None
+
+    @property
+    def loss(self):
+        """HF's ``CrossEntropyLoss()(logits.view(-1, V), labels.reshape(-1))``: the mean of -log softmax(logits)[label]
+        over the positions whose label is not -100, by torch ops on the f32 logits (no copy of them: a log-sum-exp
+        and a gather); None without labels."""
+        if self._labels is None:
+            return None
+        if self._loss is None:
+            with torch.no_grad():
+                valid = self._labels != -100
+                picked = self.logits.gather(-1, self._labels.clamp(min=0).unsqueeze(-1)).squeeze(-1)
+                nll = (torch.logsumexp(self.logits, -1) - picked) * valid
+                self._loss = nll.sum() / valid.sum()
+        return self._loss
+
+    def keys(self):
+        return [k for k in ("loss", "logits", "encoder_last_hidden_state") if getattr(self, k) is not None]
+
+    def to_tuple(self):
+        return tuple(getattr(self, k) for k in self.keys())
+
+    def __getitem__(self, i):
+        return getattr(self, i) if isinstance(i, str) else self.to_tuple()[i]
+
+    def __iter__(self):  # (a ModelOutput is a dict: iterating gives its keys)
+        return iter(self.keys())
+
+    def __len__(self):
+        return len(self.keys())
+
+
 class _Encoder:
     """``model.get_encoder()``: returns (B, 1500, d) last_hidden_state (modeling_whisper.py:592-646)."""
 
@@ -134,6 +187,9 @@ class KWhisperForConditionalGeneration:
         self.generation_config = engine.generation_config
         self._sessions = {}
         self._spec_sessions = {}  # id(assistant engine) -> the paired SpecDecodeSession
+        self._fwd_sessions = {}  # batch size -> forward()'s own DecodeSession
+        # validation: "wide" / "chunk" forces the bf16 engine's many-row plan of forward() (None: by the row count)
+        self.forward_plan = None
         self.stats = {}
         # True: generate() also keeps every seek pass's decoded ids in stats["pass_ids"] (validation: a fixture of the
         # engine's own multi-pass trajectory, tools/dump_hipmel.py)
@@ -240,6 +296,81 @@ class KWhisperForConditionalGeneration:
         if key not in self._spec_sessions:
             self._spec_sessions[key] = (SpecDecodeSession(self.engine, assistant.engine), assistant.engine)
         return self._spec_sessions[key][0]
+
+    # ---- forward (the teacher's no-grad pass of a distillation step) -------------------------------
+    def forward(self, input_features=None, attention_mask=None, decoder_input_ids=None, encoder_outputs=None,
+                labels=None, **unsupported):
+        """``WhisperForConditionalGeneration.forward`` (TF modeling_whisper.py, transformers 5.15.0) for inference:
+        what kotoba-whisper's ``train_step`` asks of its frozen teacher, ``teacher_model(**batch)`` or
+        ``teacher_model(encoder_outputs=..., labels=...)`` (run_distillation.py:641-657).
+
+        ``decoder_input_ids`` is used as given; without it the labels are shifted right behind
+        ``decoder_start_token_id`` with -100 replaced by ``pad_token_id`` (``shift_tokens_right``).  ``attention_mask``
+        is accepted and ignored (the reference's encoder reads it for SpecAugment only).  ``encoder_outputs``: what
+        ``generate(encoder_outputs=)`` takes -- a tensor, a tuple or an object with ``last_hidden_state``.  Any
+        other keyword that is not None raises ``NotImplementedError``.
+
+        Returns a ``ForwardOutput``: ``.logits`` f32 [B, T, V] on the device -- always f32, where the reference's
+        bf16 model returns bf16 -- ``.encoder_last_hidden_state`` and ``.loss`` (HF's cross-entropy over ``labels``,
+        computed on first access; None without labels).  Never builds an autograd graph."""
+        for k, v in unsupported.items():
+            if v is not None:
+                raise NotImplementedError(f"`{k}` is not supported by the MI355X engine's forward()")
+        s = self.engine.shape
+        if labels is not None:
+            if labels.shape[1] > s.max_target_positions:
+                raise ValueError(f"Labels' sequence length {labels.shape[1]} cannot exceed the maximum allowed length "
+                                 f"of {s.max_target_positions} tokens.")
+            if decoder_input_ids is None:
+                decoder_input_ids = shift_tokens_right(labels, s.pad_token_id, s.decoder_start_token_id)
+        if decoder_input_ids is None:  # (WhisperDecoder.forward's check, with no decoder_inputs_embeds to offer)
+            raise ValueError("You cannot specify both decoder_input_ids and decoder_inputs_embeds at the same time")
+        if input_features is None and encoder_outputs is None:
+            raise ValueError("Make sure to provide either `input_features` or `encoder_outputs` to `forward`.")
+        if decoder_input_ids.dim() != 2 or not 1 <= decoder_input_ids.shape[1] <= s.max_target_positions:
+            raise ValueError(f"`decoder_input_ids` must be (batch, 1 .. {s.max_target_positions})")
+        eng = self.engine
+        if getattr(eng, "cross_kv_fp8", False):
+            raise NotImplementedError("forward() is not supported with cross_kv_dtype='fp8_e4m3' (there is no many-row "
+                                      "fp8 cross-attention kernel); use the bf16 cache")
+        with torch.no_grad():
+            ids = decoder_input_ids.to(device=eng.device, dtype=torch.int64)
+            B = ids.shape[0]
+            if bool(((ids < 0) | (ids >= s.vocab_size)).any()):  # (the embedding gathers by id: never out of the table)
+                raise IndexError(f"`decoder_input_ids` must lie in [0, {s.vocab_size})")
+            if encoder_outputs is None:
+                if input_features.shape[0] != B:
+                    raise ValueError("`input_features` and `decoder_input_ids` must share the batch size")
+                enc = eng.encode(input_features.to(device=eng.device, dtype=torch.float32))
+            else:  # (given encoder outputs are used and the encoder skipped, with or without input_features, as HF does)
+                eh = encoder_outputs.last_hidden_state if hasattr(encoder_outputs, "last_hidden_state") else \
+                    encoder_outputs[0] if isinstance(encoder_outputs, (tuple, list)) else encoder_outputs
+                if eh.dim() != 3 or tuple(eh.shape) != (B, s.max_source_positions, s.d_model):
+                    raise ValueError(f"`encoder_outputs` must be ({B}, {s.max_source_positions}, {s.d_model})")
+                enc = eh.to(eng.device, eng.dtype).reshape(B * s.max_source_positions, s.d_model).contiguous()
+            sess = self._forward_session(B)
+            sess.set_encoder_output(enc)
+            logits = sess.forward_all(ids, plan=self.forward_plan)
+            # (the encoder's output buffer is the engine's: the caller gets a tensor of its own)
+            enc_out = enc.view(B, s.max_source_positions, s.d_model).clone()
+        return ForwardOutput(logits, enc_out, None if labels is None else labels.to(eng.device))
+
+    __call__ = forward
+
+    FORWARD_SESSIONS = 2  # batch sizes whose forward() session stays alive (an epoch's batch size and its last batch)
+
+    def _forward_session(self, B):
+        """forward()'s decode session of batch size B: its own, so that nothing generate() reads (ids, caches, cross
+        K/V, step buffers, captured graphs) is touched by a forward in between.  The ``FORWARD_SESSIONS`` most recently
+        used batch sizes keep theirs (about 10 GB at large-v3, B = 32); an older one is released."""
+        fs = self._fwd_sessions
+        sess = fs.pop(B, None)
+        if sess is None:
+            while len(fs) >= self.FORWARD_SESSIONS:
+                del fs[next(iter(fs))]  # the least recently used (dicts keep insertion order)
+            sess = self.engine.new_session(B)
+        fs[B] = sess
+        return sess
 
     def generate(self, input_features=None, generation_config=None, logits_processor=None, stopping_criteria=None,
                  return_timestamps=None, task=None, language=None, is_multilingual=None, attention_mask=None,

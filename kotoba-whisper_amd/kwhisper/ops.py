@@ -72,7 +72,7 @@ def _ws_bytes(kind: str, *dims) -> int:
     fn = {"dec_linear": "kw_dec_linear_workspace_bytes", "packed_weight": "kw_packed_weight_bytes",
           "self_attn": "kw_self_attn_workspace", "cross_attn": "kw_cross_attn_workspace",
           "greedy_step": "kw_greedy_step_workspace", "sample_step": "kw_sample_step_workspace", "beam_logprobs": "kw_beam_logprobs_workspace",
-          "lm_greedy": "kw_dec_lm_greedy_workspace", "dtw": "kw_dtw_workspace", "spec_accept": "kw_spec_accept_workspace",
+          "lm_greedy": "kw_dec_lm_greedy_workspace", "dtw": "kw_dtw_workspace", "kd_loss": "kw_kd_loss_workspace", "spec_accept": "kw_spec_accept_workspace",
           "qkv_self": "kw_dec_qkv_self_workspace", "xq_cross": "kw_dec_xq_cross_workspace",
           "qkv_self_status": "kw_dec_qkv_self_status_offset", "xq_cross_status": "kw_dec_xq_cross_status_offset",
           "cross_attn_status": "kw_cross_attn_status_offset"}[kind]
@@ -316,6 +316,21 @@ def pack_weight(W: torch.Tensor) -> torch.Tensor:
         _kw().pack_weight(W, out)
     else:
         L.check(_lib().kw_pack_weight(_p(W), n, k, _p(out), _s()), "kw_pack_weight")
+    return out
+
+
+def unpack_weight(packed: torch.Tensor, N: int, K: int, rows: int | None = None) -> torch.Tensor:
+    """The inverse of ``pack_weight``: the row-major bf16 [N][K] weight of a packed one (kw_gemm's W operand), as
+    ``rows`` >= N rows of which those beyond N are zero.  A pure index permutation, run once per weight: fragment
+    (column block cb of 16 rows, k-tile kt) holds, in lane l, the 8 elements k = 32 kt + 8 (l // 16) .. of row
+    16 cb + l % 16."""
+    _cuda(packed)
+    if packed.dtype != torch.bfloat16 or K % 32 or packed.numel() != _ws_bytes("packed_weight", N, K) // 2:
+        raise ValueError("unpack_weight expects pack_weight's output for (N, K)")
+    cb = packed.numel() // (16 * K)
+    w = packed.view(cb, K // 32, 4, 16, 8).permute(0, 3, 1, 2, 4).reshape(cb * 16, K)
+    out = torch.zeros((max(N, rows or N), K), device=packed.device, dtype=torch.bfloat16)
+    out[:N] = w[:N]
     return out
 
 
@@ -1077,3 +1092,54 @@ def dtw(matrix, frames=None, out=None, workspace=None):
     L.check(_lib().kw_dtw(_p(matrix), B, T, S, _p(frames), _p(out), _p(workspace),
                           workspace.numel() * workspace.element_size(), _s()), "kw_dtw")
     return out
+
+
+_KD_WS = {}  # (device index, stream handle) -> kd_loss's default workspace
+
+
+def kd_loss_workspace_bytes(N: int) -> int:
+    return _ws_bytes("kd_loss", N)
+
+
+def kd_loss(teacher, student, labels, temperature, grad=None, row_kl=None, loss=None, workspace=None):
+    """``kw_kd_loss``: the temperature KL of run_distillation.py:614-622,652-657 on logits [N][V] (row stride >= V,
+    unit inner stride; rows need no alignment).  teacher f32, student f32 or bf16, labels int64 [N] (negative =
+    ignored row).  Returns (loss f32 [1], row_kl f32 [N]); ``grad`` ([N][V], the student's dtype), when given, takes
+    d loss / d student = T (q - p) / n_valid.  Nothing synchronises with the host."""
+    _cuda(teacher, student, labels, grad, row_kl, loss, workspace)
+    if teacher.dim() != 2 or teacher.dtype != torch.float32 or teacher.stride(1) != 1:
+        raise ValueError("kw_kd_loss: teacher must be an (N, V) float32 tensor with unit inner stride")
+    N, V = teacher.shape
+    if student.dim() != 2 or tuple(student.shape) != (N, V) or student.stride(1) != 1:
+        raise ValueError("kw_kd_loss: student must be an (N, V) tensor like teacher, with unit inner stride")
+    sdt = _dt(student)
+    if labels.dim() != 1 or labels.shape[0] != N or labels.dtype != torch.int64 or not labels.is_contiguous():
+        raise ValueError("kw_kd_loss: labels must be a contiguous int64 [N] tensor")
+    if grad is not None and (grad.dim() != 2 or tuple(grad.shape) != (N, V) or grad.stride(1) != 1
+                             or grad.dtype != student.dtype):
+        raise ValueError("kw_kd_loss: grad must be an (N, V) tensor of the student's dtype with unit inner stride")
+    if N < 1 or V < 1:
+        raise ValueError("kw_kd_loss: 1 <= N, V < 2^31 and every row stride >= V")
+    dev = teacher.device
+    if row_kl is None:
+        row_kl = torch.empty((N,), device=dev, dtype=torch.float32)
+    if loss is None:
+        loss = torch.empty((1,), device=dev, dtype=torch.float32)
+    if (row_kl.dtype != torch.float32 or not row_kl.is_contiguous() or row_kl.numel() != N
+            or loss.dtype != torch.float32 or loss.numel() != 1):
+        raise ValueError("kw_kd_loss: row_kl float32 [N], loss float32 [1]")
+    if workspace is None:
+        # zero-filled once per (device, stream) and kept: calls leave it zeroed, and calls on one stream are ordered
+        key = (dev.index, torch.cuda.current_stream(dev).cuda_stream)
+        workspace = _KD_WS.get(key)
+        if workspace is None or workspace.numel() < kd_loss_workspace_bytes(N):
+            workspace = _KD_WS[key] = torch.zeros((kd_loss_workspace_bytes(N),), device=dev, dtype=torch.uint8)
+    if _BACKEND == "torch":
+        _kw().kd_loss(teacher, student, labels, float(temperature), row_kl, loss, grad, workspace)
+        return loss, row_kl
+    ld = (lambda t: V if N == 1 else t.stride(0))  # (a one-row tensor's stride(0) is arbitrary)
+    a = L.KdLossArgs(_p(teacher), ld(teacher), _p(student), ld(student), sdt, _p(labels), N, V, float(temperature),
+                     _p(row_kl), _p(loss), _p(grad), 0 if grad is None else ld(grad), _p(workspace),
+                     workspace.numel() * workspace.element_size())
+    L.check(_lib().kw_kd_loss(ctypes.byref(a), _s()), "kw_kd_loss")
+    return loss, row_kl
