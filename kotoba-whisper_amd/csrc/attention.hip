@@ -15,15 +15,20 @@
 // Decoder self-attention (K10): static KV cache append + attention; one new position per row splits
 //   the keys into <= 256-key chunks like the cross-attention (prefill, q_len > 1: one workgroup per
 //   (b, h) walking the queries).  kw_self_attn_step_masked: the same with a per-row first key (left-padded
-//   prompts of a conditioned long-form pass), kernels of their own -- self_attn_step1_masked (chunks start at
-//   the row's first key), self_attn_prefill_masked (f32: one workgroup per (b, h, query position), a prompt of
-//   ~228 positions runs side by side) and self_attn_prefill_masked_mfma (bf16: one wave per 16 query positions,
-//   S^T = K Q^T and O^T = V^T P^T on v_mfma_f32_16x16x32_bf16 over 32-key tiles).
+//   prompts of a conditioned long-form pass).  Its kernels are thin entries over the unmasked kernels' code:
+//   self_attn_step1_masked is self_step1_body with the chunks starting at the row's first key,
+//   self_attn_prefill_masked (f32) is self_attn_step's per-query work (self_attend_query) with one workgroup
+//   per (b, h, query position), so a prompt of ~228 positions runs side by side.  Only
+//   self_attn_prefill_masked_mfma is code of its own (bf16: one wave per 16 query positions, S^T = K Q^T and
+//   O^T = V^T P^T on v_mfma_f32_16x16x32_bf16 over 32-key tiles).
 // Decoder cross-attention (K11): split-S partial softmax over cached encoder K/V in <= 256-key chunks,
 //   8 lanes per key row so every K and V load is a coalesced 1-KB wave access, and every load of the
 //   chunk (64 KB) issued before the first score; the last-arriving chunk combines the partials in the
 //   same launch (write-through partials + arrival counter, MI355X_MICROARCH "Valid forms" row 1).
 #include <math.h>
+#include <stdio.h>
+
+#include <type_traits>
 
 #include "attn_common.h"
 #include "decproj.h"
@@ -883,6 +888,36 @@ __device__ __forceinline__ void wave_partials_combine(unsigned long long* gr, in
 // New keys/values are read from the qkv rows themselves (never read back from the cache in the
 // same launch).
 // ------------------------------------------------------------------------------------------------
+// the append of one new position of (b, h), qkv row qrow (its q; k at + d, v at + 2 d), cache row pos: thread
+// c8 < 8 copies 16 B of its k and of its v
+template <typename T>
+__device__ __forceinline__ void self_append_row(const T* qrow, int d, int c8, T* kb, T* vb, int pos) {
+  const T* row = qrow + c8 * 8;
+  copy8<T>(kb + (int64_t)pos * HD + c8 * 8, row + d);
+  copy8<T>(vb + (int64_t)pos * HD + c8 * 8, row + 2 * d);
+}
+
+// One query position of (b, h) by the whole workgroup, when the launch's q_len new positions start at p0: the
+// query in qkv row qrow attends the keys [k_begin, k_end) -- cache rows (kb, vb) below p0, the launch's own qkv
+// rows from p0 -- in attend_rows' order, and the normalised row goes to orow() (formed at the store).
+template <typename T, typename OutRow>
+__device__ __forceinline__ void self_attend_query(const T* qkv, int q_len, int d, int b, int h, const T* qrow, OutRow orow,
+                                                  const T* kb, const T* vb, int p0, int k_begin, int k_end, float* sc,
+                                                  float (*red)[65], float* stat) {
+  const int tid = threadIdx.x, sub = tid & 7;
+  auto kp = [&](int k) -> const T* {
+    return k < p0 ? kb + (int64_t)k * HD : qkv + ((int64_t)b * q_len + (k - p0)) * 3 * d + d + h * HD;
+  };
+  auto vp = [&](int k) -> const T* {
+    return k < p0 ? vb + (int64_t)k * HD : qkv + ((int64_t)b * q_len + (k - p0)) * 3 * d + 2 * d + h * HD;
+  };
+  float qv[8];
+  load8<T>(qrow + sub * 8, qv);
+  float m, l, o;
+  attend_rows<T>(qv, k_begin, k_end, kp, vp, sc, red, stat, m, l, o);
+  if (tid < HD) TypeIO<T>::st(orow() + tid, o / l);
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void self_attn_step(const T* __restrict__ qkv, int q_len, int H, T* __restrict__ kc,
                                                       T* __restrict__ vc, int t_max, const int32_t* __restrict__ cur_len,
@@ -892,31 +927,18 @@ __global__ __launch_bounds__(256) void self_attn_step(const T* __restrict__ qkv,
   __shared__ float stat[8];
   const int bh = blockIdx.x;
   const int b = bh / H, h = bh - (bh / H) * H;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int sub = lane & 7;
+  const int tid = threadIdx.x;
   const int L = *cur_len;
   const int d = H * HD;
   const int p0 = L - q_len;
   T* kb = kc + ((int64_t)b * H + h) * t_max * HD;
   T* vb = vc + ((int64_t)b * H + h) * t_max * HD;
-  for (int i = tid; i < q_len * 8; i += 256) {
-    const int qi = i >> 3, c8 = i & 7;
-    const T* row = qkv + ((int64_t)b * q_len + qi) * 3 * d + h * HD + c8 * 8;
-    copy8<T>(kb + (int64_t)(p0 + qi) * HD + c8 * 8, row + d);
-    copy8<T>(vb + (int64_t)(p0 + qi) * HD + c8 * 8, row + 2 * d);
-  }
-  auto kp = [&](int k) -> const T* {
-    return k < p0 ? kb + (int64_t)k * HD : qkv + ((int64_t)b * q_len + (k - p0)) * 3 * d + d + h * HD;
-  };
-  auto vp = [&](int k) -> const T* {
-    return k < p0 ? vb + (int64_t)k * HD : qkv + ((int64_t)b * q_len + (k - p0)) * 3 * d + 2 * d + h * HD;
-  };
+  auto qrow = [&](int qi) -> const T* { return qkv + ((int64_t)b * q_len + qi) * 3 * d + h * HD; };
+  for (int i = tid; i < q_len * 8; i += 256) self_append_row<T>(qrow(i >> 3), d, i & 7, kb, vb, p0 + (i >> 3));
   for (int qi = 0; qi < q_len; ++qi) {
-    float qv[8];
-    load8<T>(qkv + ((int64_t)b * q_len + qi) * 3 * d + h * HD + sub * 8, qv);
-    float m, l, o;
-    attend_rows<T>(qv, 0, p0 + qi + 1, kp, vp, sc, red, stat, m, l, o);
-    if (tid < HD) TypeIO<T>::st(out + ((int64_t)b * q_len + qi) * d + h * HD + tid, o / l);
+    self_attend_query<T>(
+        qkv, q_len, d, b, h, qrow(qi), [&] { return out + ((int64_t)b * q_len + qi) * d + h * HD; }, kb, vb, p0, 0,
+        p0 + qi + 1, sc, red, stat);
     __syncthreads();
   }
 }
@@ -1163,11 +1185,14 @@ __device__ __forceinline__ void row_fold(float mw, const float (&sc)[8], const P
   for (int i = 0; i < 8; ++i) A[i] = fold_value(mode, A[i], acc[i], f0, f1);
 }
 
-template <bool QG, int NS>  // NS chunks per pair (6 for Whisper's 1500 frames): a static schedule, static load counts
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void cross_attn_row_kernel(CRP p) {
-  __shared__ __attribute__((aligned(16))) char scratch[QG ? PROJ_SCRATCH : 16];
-  __shared__ float red[4][64];
-  __shared__ float stat[8];
+// The pair kernel's body, for both caches: P = u32x4 pieces over the bf16 cache (CRP, cross_attn_row_kernel), P =
+// u32x2 pieces of e4m3 codes over the fp8 cache (CRP8, cross_attn_row_fp8_kernel; what only that cache needs sits
+// under `if constexpr (F8)`).  NS chunks per pair (6 for Whisper's 1500 frames): a static schedule, static load counts.
+template <bool QG, int NS, typename P, typename Params>
+__device__ __forceinline__ void cross_row_pair(const Params p, char* scratch, float (*red)[64], float* stat) {
+  constexpr bool F8 = sizeof(P) == 8;
+  using El = std::conditional_t<F8, uint8_t, bf16_t>;  // a cache element
+  constexpr int EB = sizeof(El);
   if constexpr (QG) {
     if ((int)blockIdx.x < p.n_lin) {
       proj_publish_granules<true>(p.proj, blockIdx.x, scratch, p.qg);
@@ -1176,105 +1201,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
   }
   const int row = blockIdx.x - (QG ? p.n_lin : 0);
   const int h = row % p.H, b = row / p.H;
-  const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int sub = lane & 7, slot = wave * 8 + (lane >> 3);
-  const bf16_t* kb = p.kc + ((int64_t)b * p.H + h) * p.S * HD;
-  const bf16_t* vb = p.vc + ((int64_t)b * p.H + h) * p.S * HD;
-  unsigned long long* qg = QG ? p.qg + (int64_t)b * (p.d / 2) + h * 32 : nullptr;
-  // the query's loads first, then the first two chunks' K / V
-  unsigned long long g[4];
-  u32x4 qraw;
-  if constexpr (QG) {
-#pragma unroll
-    for (int i = 0; i < 4; ++i) g[i] = peek_granule(qg + sub * 4 + i);
-  } else {
-    qraw = *reinterpret_cast<const u32x4*>(p.q + (int64_t)b * p.d + h * HD + sub * 8);
-  }
-  constexpr int ns = NS;
-  const int chunk = p.chunk, S = p.S;
-  const __amdgpu_buffer_rsrc_t rsk = __builtin_amdgcn_make_buffer_rsrc((void*)kb, (short)0, S * HD * 2, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc((void*)vb, (short)0, S * HD * 2, 0x00020000);
-  const uint32_t voff = (uint32_t)((slot * HD + sub * 8) * 2);
-  // three 32-register K / V sets in rotation: chunk c + 1's K goes out before chunk c's scores, its V right
-  // after them (into chunk c's dead K registers), chunk c + 2's K after chunk c's values (into its dead V
-  // registers) -- one chunk in flight while one is computed, 96 K / V registers live
-  u32x4 r0[8], r1[8], r2[8];
-  row_issue(rsk, 0, voff, r0);
-  row_issue(rsv, 0, voff, r1);
-  if (ns > 1) row_issue(rsk, chunk, voff, r2);
-  if constexpr (QG) qraw = wait_query_granules(qg + sub * 4, g, p.err);
-  float ql[8];
-  query_log2(qraw, ql);
-  float M = -INFINITY, Lr = 0.f, A[8];
-#pragma unroll
-  for (int i = 0; i < 8; ++i) A[i] = 0.f;
-  // chunk c: K in rk, V in rv (the next chunk's K already in the third set); after the step V(c + 1) is in rk
-  // and K(c + 2) in rv
-  auto step = [&](const int c, u32x4 (&rk)[8], u32x4 (&rv)[8]) __attribute__((always_inline)) {
-    float sc[8];
-    const int k0 = c * chunk, k1 = min(S, k0 + chunk);
-    const float mw = wave_scores_bf16<32, ROW_JV>(ql, rk, k0, k1, slot, 8, sc);
-    if (c + 1 < ns) row_issue(rsv, k1, voff, rk);
-    row_fold(mw, sc, rv, k0, k1, slot, M, Lr, A);
-    if (c + 2 < ns) row_issue(rsk, k0 + 2 * chunk, voff, rv);
-  };
-#pragma unroll
-  for (int c = 0; c < ns; c += 3) {
-    step(c, r0, r1);                      // K(c) r0, V(c) r1 -> V(c+1) r0, K(c+2) r1
-    if (c + 1 < ns) step(c + 1, r2, r0);  // K(c+1) r2, V(c+1) r0 -> V(c+2) r2, K(c+3) r0
-    if (c + 2 < ns) step(c + 2, r1, r2);  // K(c+2) r1, V(c+2) r2 -> V(c+3) r1, K(c+4) r2
-  }
-  if (lane < 8) {
-#pragma unroll
-    for (int i = 0; i < 8; ++i) red[wave][lane * 8 + i] = A[i];
-  }
-  if (lane == 0) {
-    stat[wave] = M;
-    stat[4 + wave] = Lr;
-  }
-  __syncthreads();
-  float m, l, o;
-  merge_waves_bf16(stat, red, tid, m, l, o);
-  if (tid < HD) TypeIO<bf16_t>::st(p.out + (p.out_t ? kw_tiled_off(b, h * HD + tid, p.out_t) : (int64_t)b * p.d + h * HD + tid), o / l);
-  if constexpr (QG) {
-    if (tid < 32)  // re-arm the row's query for the next launch (every wave of this, its only reader, has read it)
-      __hip_atomic_store(qg + tid, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  }
-}
-
-// ------------------------------------------------------------------------------------------------
-// The same pair kernel over the fp8 (e4m3) cross cache (include/kwhisper.h "fp8 cross K/V"): the only grid of
-// kw_cross_attn_step_fp8 / kw_dec_xq_cross_fp8, at every batch size (a row's output then cannot depend on its batch)
-// and for q_len > 1 (one pair per query row and head, each reading its own item's K / V).  Lanes, key slots and
-// arithmetic are cross_attn_row_kernel's, through the same helpers on 8-byte pieces of codes (row_dims decodes them):
-// each wave folds its chunks with row_fold, the four waves merge once with merge_waves_bf16, the query comes from
-// memory or (QG) from the projection workgroups through wait_query_granules.  The pair's 64 K scales multiply the
-// query once, before the first score (8 per lane, loaded with the query), its V scales the output at the final
-// store: no scale is loaded per key.
-// The rotation is the bf16 kernel's too: three sets of 8 pieces (16 registers each here), one chunk in flight while one
-// is computed.  Five sets with two chunks in flight (the registers are there) measured no faster -- 29.2 against 28.9
-// us per launch, profiles/fp8_cross_kbench.txt -- so the bytes in flight do not bound this kernel.
-template <bool QG, int NS>
-__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void cross_attn_row_fp8_kernel(CRP8 p) {
-  using P = u32x2;
-  __shared__ __attribute__((aligned(16))) char scratch[QG ? PROJ_SCRATCH : 16];
-  __shared__ float red[4][64];
-  __shared__ float stat[8];
-  if constexpr (QG) {
-    if ((int)blockIdx.x < p.n_lin) {
-      proj_publish_granules<true>(p.proj, blockIdx.x, scratch, p.qg);
-      return;
-    }
-  }
-  const int row = blockIdx.x - (QG ? p.n_lin : 0);
-  const int h = row % p.H, b = row / p.H, item = b / p.q_len;
+  int item = b;  // the K / V (and scales) of query row b: with q_len rows per item, item b / q_len's
+  if constexpr (F8) item = b / p.q_len;
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int sub = lane & 7, slot = wave * 8 + (lane >> 3);
   const int64_t pair = (int64_t)item * p.H + h;
-  const uint8_t* kb = reinterpret_cast<const uint8_t*>(p.kc) + pair * p.S * HD;
-  const uint8_t* vb = reinterpret_cast<const uint8_t*>(p.vc) + pair * p.S * HD;
+  const El* kb = reinterpret_cast<const El*>(p.kc) + pair * p.S * HD;
+  const El* vb = reinterpret_cast<const El*>(p.vc) + pair * p.S * HD;
   unsigned long long* qg = QG ? p.qg + (int64_t)b * (p.d / 2) + h * 32 : nullptr;
-  // the query's loads and the lane's 8 K scales first, then the first two chunks' K / V
+  // the query's loads first (fp8: and the lane's 8 K scales), then the first two chunks' K / V
   unsigned long long g[4];
   u32x4 qraw;
   if constexpr (QG) {
@@ -1283,13 +1218,21 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
   } else {
     qraw = *reinterpret_cast<const u32x4*>(p.q + (int64_t)b * p.d + h * HD + sub * 8);
   }
-  const f32x4* ks4 = reinterpret_cast<const f32x4*>(p.ks + pair * HD + sub * 8);
-  const f32x4 ksc[2] = {ks4[0], ks4[1]};
+  [[maybe_unused]] f32x4 ksc[2];
+  if constexpr (F8) {
+    const f32x4* ks4 = reinterpret_cast<const f32x4*>(p.ks + pair * HD + sub * 8);
+    ksc[0] = ks4[0], ksc[1] = ks4[1];
+  }
   constexpr int ns = NS;
   const int chunk = p.chunk, S = p.S;
-  const __amdgpu_buffer_rsrc_t rsk = __builtin_amdgcn_make_buffer_rsrc((void*)kb, (short)0, S * HD, 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc((void*)vb, (short)0, S * HD, 0x00020000);
-  const uint32_t voff = (uint32_t)(slot * HD + sub * 8);
+  const __amdgpu_buffer_rsrc_t rsk = __builtin_amdgcn_make_buffer_rsrc((void*)kb, (short)0, S * HD * EB, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsv = __builtin_amdgcn_make_buffer_rsrc((void*)vb, (short)0, S * HD * EB, 0x00020000);
+  const uint32_t voff = (uint32_t)((slot * HD + sub * 8) * EB);
+  // three sets of 8 pieces (32 registers each for bf16, 16 for fp8) in rotation: chunk c + 1's K goes out before
+  // chunk c's scores, its V right after them (into chunk c's dead K registers), chunk c + 2's K after chunk c's
+  // values (into its dead V registers) -- one chunk in flight while one is computed, 96 K / V registers live (bf16).
+  // Five sets with two chunks in flight (fp8: the registers are there) measured no faster -- 29.2 against 28.9 us per
+  // launch, profiles/fp8_cross_kbench.txt -- so the bytes in flight do not bound this kernel.
   P r0[8], r1[8], r2[8];
   row_issue(rsk, 0, voff, r0);
   row_issue(rsv, 0, voff, r1);
@@ -1297,8 +1240,10 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
   if constexpr (QG) qraw = wait_query_granules(qg + sub * 4, g, p.err);
   float ql[8];
   query_log2(qraw, ql);
+  if constexpr (F8) {  // the pair's K scales multiply the query once, before the first score
 #pragma unroll
-  for (int i = 0; i < 8; ++i) ql[i] *= ksc[i >> 2][i & 3];
+    for (int i = 0; i < 8; ++i) ql[i] *= ksc[i >> 2][i & 3];
+  }
   float M = -INFINITY, Lr = 0.f, A[8];
 #pragma unroll
   for (int i = 0; i < 8; ++i) A[i] = 0.f;
@@ -1329,13 +1274,36 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void c
   __syncthreads();
   float m, l, o;
   merge_waves_bf16(stat, red, tid, m, l, o);
-  if (tid < HD)
-    TypeIO<bf16_t>::st(p.out + (p.out_t ? kw_tiled_off(b, h * HD + tid, p.out_t) : (int64_t)b * p.d + h * HD + tid),
-                       o * p.vs[pair * HD + tid] / l);
+  if (tid < HD) {
+    if constexpr (F8) o *= p.vs[pair * HD + tid];  // the pair's V scales, once, at the store
+    TypeIO<bf16_t>::st(p.out + (p.out_t ? kw_tiled_off(b, h * HD + tid, p.out_t) : (int64_t)b * p.d + h * HD + tid), o / l);
+  }
   if constexpr (QG) {
     if (tid < 32)  // re-arm the row's query for the next launch (every wave of this, its only reader, has read it)
       __hip_atomic_store(qg + tid, 0ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
+}
+
+template <bool QG, int NS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void cross_attn_row_kernel(CRP p) {
+  __shared__ __attribute__((aligned(16))) char scratch[QG ? PROJ_SCRATCH : 16];
+  __shared__ float red[4][64];
+  __shared__ float stat[8];
+  cross_row_pair<QG, NS, u32x4>(p, scratch, red, stat);
+}
+
+// ------------------------------------------------------------------------------------------------
+// The same pair kernel over the fp8 (e4m3) cross cache (include/kwhisper.h "fp8 cross K/V"): the only grid of
+// kw_cross_attn_step_fp8 / kw_dec_xq_cross_fp8, at every batch size (a row's output then cannot depend on its batch)
+// and for q_len > 1 (one pair per query row and head, each reading its own item's K / V).  The body is
+// cross_row_pair on 8-byte pieces of codes (row_dims decodes them).  The pair's 64 K scales multiply the query
+// once (8 per lane, loaded with the query), its V scales the output at the final store: no scale is loaded per key.
+template <bool QG, int NS>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(3))) void cross_attn_row_fp8_kernel(CRP8 p) {
+  __shared__ __attribute__((aligned(16))) char scratch[QG ? PROJ_SCRATCH : 16];
+  __shared__ float red[4][64];
+  __shared__ float stat[8];
+  cross_row_pair<QG, NS, u32x2>(p, scratch, red, stat);
 }
 
 // Cross-attention for several query rows of one item (the prefill's P prompt positions, and the beams of
@@ -1699,31 +1667,42 @@ __global__ __launch_bounds__(256) void cross_attn_mfma_kernel(const bf16_t* __re
 }
 
 // decoder self-attention for one new position (q_len == 1): split 0 appends k/v at L-1; each split
-// attends over its <= 256-key chunk of [0, L) (the new row read from qkv, never from the cache in the
-// same launch); splits beyond L exit; the last arriving split combines.
-template <typename T, bool BP>
-__global__ __launch_bounds__(256) void self_attn_step1(const T* __restrict__ qkv, int H, T* __restrict__ kc,
-                                                       T* __restrict__ vc, int t_max, const int32_t* __restrict__ cur_len,
-                                                       const int32_t* __restrict__ bp, int bp_stride,
-                                                       float* __restrict__ ws, int* __restrict__ cnt, T* __restrict__ out) {
-  __shared__ float red[4][64];
-  __shared__ float stat[8];
-  __shared__ int last;
+// attends over its <= 256-key chunk of [ks, L) (the new row read from qkv, never from the cache in the
+// same launch); splits beyond L exit; the last arriving split combines.  ks = 0 (self_attn_step1), or with
+// MASKED the row's first key, key_start[b] (self_attn_step1_masked: left-padded prompts) -- the chunks start at
+// ks, the keys below are never read, and ks == 0 gives the unmasked chunks and bits.  L - ks <= t_max <= 512: at
+// most two chunks, the workspace of kw_self_attn_workspace.  MASKED and ks >= L (a pad position, no key): the
+// position is appended all the same and the output row is zero.
+template <typename T, bool BP, bool MASKED>
+__device__ __forceinline__ void self_step1_body(const T* qkv, int H, T* kc, T* vc, int t_max, const int32_t* cur_len,
+                                                const int32_t* key_start, const int32_t* bp, int bp_stride, float* ws,
+                                                int* cnt, T* out, float (*red)[64], float* stat, int* last) {
   const int bh = blockIdx.x, split = blockIdx.y;
   const int b = bh / H, h = bh - (bh / H) * H;
   const int tid = threadIdx.x, sub = tid & 7;
   const int L = *cur_len;
   const int d = H * HD;
   const int p0 = L - 1;
-  const int k0 = split * 256;
-  if (k0 >= L) return;
-  const int ns = (L + 255) / 256;
+  int ks = 0;
+  if constexpr (MASKED) ks = max(key_start[b], 0);
+  const int k0 = ks + split * 256;
+  if constexpr (!MASKED) {
+    if (k0 >= L) return;
+  }
+  const int ns = (L - ks + 255) / 256;
   T* kb = kc + ((int64_t)b * H + h) * t_max * HD;
   T* vb = vc + ((int64_t)b * H + h) * t_max * HD;
   const T* row = qkv + (int64_t)b * 3 * d + h * HD;
+  T* orow = out + (int64_t)b * d + h * HD;
   if (split == 0 && tid < 8) {
     copy8<T>(kb + (int64_t)p0 * HD + tid * 8, row + d + tid * 8);
     copy8<T>(vb + (int64_t)p0 * HD + tid * 8, row + 2 * d + tid * 8);
+  }
+  if constexpr (MASKED) {
+    if (k0 >= L) {
+      if (split == 0 && tid < HD) TypeIO<T>::st(orow + tid, 0.f);
+      return;
+    }
   }
   float qv[8];
   load8<T>(row + sub * 8, qv);
@@ -1747,12 +1726,22 @@ __global__ __launch_bounds__(256) void self_attn_step1(const T* __restrict__ qkv
   attend_chunk<T>(qv, k0, k1,
                   [&](int k, int j) -> const T* { return k < p0 ? kc + slot(k, j) : row + d; },
                   [&](int k, int j) -> const T* { return k < p0 ? vc + slot(k, j) : row + 2 * d; }, red, stat, m, l, o);
-  T* orow = out + (int64_t)b * d + h * HD;
   if (ns == 1) {
     if (tid < HD) TypeIO<T>::st(orow + tid, o / l);
     return;
   }
-  publish_and_combine<T>(ws + (int64_t)bh * 2 * (HD + 2), cnt + bh, ns, split, m, l, o, orow, &last);
+  publish_and_combine<T>(ws + (int64_t)bh * 2 * (HD + 2), cnt + bh, ns, split, m, l, o, orow, last);
+}
+
+template <typename T, bool BP>
+__global__ __launch_bounds__(256) void self_attn_step1(const T* __restrict__ qkv, int H, T* __restrict__ kc,
+                                                       T* __restrict__ vc, int t_max, const int32_t* __restrict__ cur_len,
+                                                       const int32_t* __restrict__ bp, int bp_stride,
+                                                       float* __restrict__ ws, int* __restrict__ cnt, T* __restrict__ out) {
+  __shared__ float red[4][64];
+  __shared__ float stat[8];
+  __shared__ int last;
+  self_step1_body<T, BP, false>(qkv, H, kc, vc, t_max, cur_len, nullptr, bp, bp_stride, ws, cnt, out, red, stat, &last);
 }
 
 // The chunk schedule of the cross-attention over S keys for `rows` (row, head) pairs: ns = ceil(S / 256) chunks of
@@ -1774,13 +1763,13 @@ struct CrossGeo {
 };
 
 // ------------------------------------------------------------------------------------------------
-// kw_self_attn_step_masked's kernels.  They stand behind every other kernel of this file so that those keep
-// their place in the code object.
+// kw_self_attn_step_masked's kernels (emitted last in the code object: launch_self_attn_masked, which
+// instantiates them, ends the file).
 // ------------------------------------------------------------------------------------------------
 // The same append and causal attention with a per-row first key (left-padded prompts: row b attends keys
 // [key_start[b], own position], the keys below are never read), one workgroup per (row, head, query position):
-// the query positions of a long prompt run side by side instead of one after the other.  A query is summed by
-// attend_rows in self_attn_step's order, so key_start == 0 gives that kernel's bits.  A query position below
+// the query positions of a long prompt run side by side instead of one after the other.  A query is
+// self_attn_step's (self_attend_query), so key_start == 0 gives that kernel's bits.  A query position below
 // its row's key_start (a pad) has no key: its output is zero.  Each workgroup appends its own position's K/V.
 template <typename T>
 __global__ __launch_bounds__(256) void self_attn_prefill_masked(const T* __restrict__ qkv, int q_len, int H,
@@ -1793,8 +1782,7 @@ __global__ __launch_bounds__(256) void self_attn_prefill_masked(const T* __restr
   __shared__ float stat[8];
   const int bh = blockIdx.x, qi = blockIdx.y;
   const int b = bh / H, h = bh - (bh / H) * H;
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int sub = lane & 7;
+  const int tid = threadIdx.x;
   const int L = *cur_len;
   const int d = H * HD;
   const int p0 = L - q_len;
@@ -1802,32 +1790,16 @@ __global__ __launch_bounds__(256) void self_attn_prefill_masked(const T* __restr
   T* kb = kc + ((int64_t)b * H + h) * t_max * HD;
   T* vb = vc + ((int64_t)b * H + h) * t_max * HD;
   const T* qrow = qkv + ((int64_t)b * q_len + qi) * 3 * d + h * HD;
-  if (tid < 8) {
-    copy8<T>(kb + (int64_t)(p0 + qi) * HD + tid * 8, qrow + d + tid * 8);
-    copy8<T>(vb + (int64_t)(p0 + qi) * HD + tid * 8, qrow + 2 * d + tid * 8);
-  }
+  if (tid < 8) self_append_row<T>(qrow, d, tid, kb, vb, p0 + qi);
   T* orow = out + ((int64_t)b * q_len + qi) * d + h * HD;
   if (ks > p0 + qi) {  // workgroup-uniform
     if (tid < HD) TypeIO<T>::st(orow + tid, 0.f);
     return;
   }
-  auto kp = [&](int k) -> const T* {
-    return k < p0 ? kb + (int64_t)k * HD : qkv + ((int64_t)b * q_len + (k - p0)) * 3 * d + d + h * HD;
-  };
-  auto vp = [&](int k) -> const T* {
-    return k < p0 ? vb + (int64_t)k * HD : qkv + ((int64_t)b * q_len + (k - p0)) * 3 * d + 2 * d + h * HD;
-  };
-  float qv[8];
-  load8<T>(qrow + sub * 8, qv);
-  float m, l, o;
-  attend_rows<T>(qv, ks, p0 + qi + 1, kp, vp, sc, red, stat, m, l, o);
-  if (tid < HD) TypeIO<T>::st(orow + tid, o / l);
+  self_attend_query<T>(qkv, q_len, d, b, h, qrow, [&] { return orow; }, kb, vb, p0, ks, p0 + qi + 1, sc, red, stat);
 }
 
-// self_attn_step1 with a per-row first key (a kernel of its own: self_attn_step1's code stays as it compiles
-// today).  Row b attends [ks, L), ks = key_start[b], in <= 256-key chunks that start at ks -- the keys below are
-// never read, and ks == 0 gives self_attn_step1's chunks and bits.  L - ks <= t_max <= 512: at most two chunks,
-// the workspace of kw_self_attn_workspace.  ks >= L (a pad position, no key): the output row is zero.
+// self_attn_step1 with a per-row first key: self_step1_body<T, BP, true>
 template <typename T, bool BP>
 __global__ __launch_bounds__(256) void self_attn_step1_masked(const T* __restrict__ qkv, int H, T* __restrict__ kc,
                                                               T* __restrict__ vc, int t_max,
@@ -1839,50 +1811,7 @@ __global__ __launch_bounds__(256) void self_attn_step1_masked(const T* __restric
   __shared__ float red[4][64];
   __shared__ float stat[8];
   __shared__ int last;
-  const int bh = blockIdx.x, split = blockIdx.y;
-  const int b = bh / H, h = bh - (bh / H) * H;
-  const int tid = threadIdx.x, sub = tid & 7;
-  const int L = *cur_len;
-  const int d = H * HD;
-  const int p0 = L - 1;
-  const int ks = max(key_start[b], 0);
-  const int k0 = ks + split * 256;
-  T* kb = kc + ((int64_t)b * H + h) * t_max * HD;
-  T* vb = vc + ((int64_t)b * H + h) * t_max * HD;
-  const T* row = qkv + (int64_t)b * 3 * d + h * HD;
-  T* orow = out + (int64_t)b * d + h * HD;
-  if (split == 0 && tid < 8) {
-    copy8<T>(kb + (int64_t)p0 * HD + tid * 8, row + d + tid * 8);
-    copy8<T>(vb + (int64_t)p0 * HD + tid * 8, row + 2 * d + tid * 8);
-  }
-  if (k0 >= L) {
-    if (split == 0 && tid < HD) TypeIO<T>::st(orow + tid, 0.f);
-    return;
-  }
-  const int ns = (L - ks + 255) / 256;
-  float qv[8];
-  load8<T>(row + sub * 8, qv);
-  float m, l, o;
-  const int k1 = min(L, k0 + 256);
-  const int kslot = (tid >> 6) * 8 + ((tid & 63) >> 3);
-  int32_t crow[8];
-  if constexpr (BP) {
-    const int32_t* bpr = bp + (int64_t)b * bp_stride;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) crow[j] = bpr[min(k0 + kslot + 32 * j, k1 - 1)];  // < L <= t_max <= bp_stride
-  } else {
-#pragma unroll
-    for (int j = 0; j < 8; ++j) crow[j] = b;
-  }
-  auto slot = [&](int k, int j) -> int64_t { return ((int64_t)crow[j] * H + h) * t_max * HD + (int64_t)k * HD; };
-  attend_chunk<T>(qv, k0, k1,
-                  [&](int k, int j) -> const T* { return k < p0 ? kc + slot(k, j) : row + d; },
-                  [&](int k, int j) -> const T* { return k < p0 ? vc + slot(k, j) : row + 2 * d; }, red, stat, m, l, o);
-  if (ns == 1) {
-    if (tid < HD) TypeIO<T>::st(orow + tid, o / l);
-    return;
-  }
-  publish_and_combine<T>(ws + (int64_t)bh * 2 * (HD + 2), cnt + bh, ns, split, m, l, o, orow, &last);
+  self_step1_body<T, BP, true>(qkv, H, kc, vc, t_max, cur_len, key_start, bp, bp_stride, ws, cnt, out, red, stat, &last);
 }
 
 // The bf16 prefill as a causal tile kernel: one wave per (row, head, 16 query positions), keys in tiles of 32 from the
@@ -2039,35 +1968,63 @@ extern "C" int kw_attention(int dtype, const void* qkv, int64_t B, int64_t H, in
   return KW_OK;
 }
 
+// The self-attention workspace of the one-position step, byte offsets: f32 chunk partials [B H][2][HD+2] (t_max <= 512:
+// at most two 256-key chunks per (b, h)) | arrival counters [B H].  Zero before first use.
+struct SelfLayout {
+  size_t counters, end;
+  SelfLayout(int64_t B, int64_t H)
+      : counters((size_t)(B * H) * 2 * (HD + 2) * sizeof(float)), end(counters + (size_t)(B * H) * sizeof(int)) {}
+  float* part(void* ws) const { return reinterpret_cast<float*>(ws); }
+  int* cnt(void* ws) const { return reinterpret_cast<int*>(reinterpret_cast<char*>(ws) + counters); }
+};
+
 extern "C" size_t kw_self_attn_workspace(int64_t B, int64_t H, int64_t t_max) {
-  (void)t_max;  // t_max <= 512: at most two 256-key chunks per (b, h)
-  return (size_t)(B * H) * 2 * (HD + 2) * sizeof(float) + (size_t)(B * H) * sizeof(int);
+  (void)t_max;
+  return SelfLayout(B, H).end;
+}
+
+// the argument checks of kw_self_attn_step and (masked: a key_start, q_len <= t_max, a dtype that is checked)
+// kw_self_attn_step_masked, reported under the entry's name `fn`
+static int self_attn_check(const char* fn, bool masked, int dtype, const void* qkv, int64_t B, int64_t q_len, int64_t H,
+                           int64_t hd, const void* k_cache, const void* v_cache, int64_t t_max, const int32_t* cur_len,
+                           const int32_t* key_start, const int32_t* bp, int64_t bp_stride, const void* out,
+                           const void* workspace, size_t ws_bytes) {
+  auto fail = [fn](int code, const char* what) {
+    char msg[192];
+    snprintf(msg, sizeof(msg), "%s: %s", fn, what);
+    return kw_set_error_msg(code, msg);
+  };
+  if (!qkv || !k_cache || !v_cache || !cur_len || !out || B <= 0 || q_len <= 0 || H <= 0 || t_max <= 0 || t_max > 512 ||
+      (masked && (!key_start || q_len > t_max)))
+    return fail(KW_EINVAL, masked ? "invalid arguments (q_len <= t_max <= 512)" : "invalid arguments (t_max <= 512)");
+  if (hd != HD) return fail(KW_EUNSUPPORTED, "head_dim must be 64");
+  if (masked && dtype != KW_DT_BF16 && dtype != KW_DT_F32) return fail(KW_EUNSUPPORTED, "dtype");
+  if (bp && (q_len != 1 || bp_stride < t_max))
+    return fail(KW_EINVAL, "a slot table needs q_len == 1 and bp_stride >= t_max");
+  if (q_len == 1 && (!workspace || ws_bytes < SelfLayout(B, H).end))
+    return fail(KW_EINVAL, "needs a zero-filled workspace of kw_self_attn_workspace()");
+  return KW_OK;
 }
 
 extern "C" int kw_self_attn_step(int dtype, const void* qkv, int64_t B, int64_t q_len, int64_t H, int64_t hd,
                                  void* k_cache, void* v_cache, int64_t t_max, const int32_t* cur_len,
                                  const int32_t* bp, int64_t bp_stride, void* out, void* workspace, size_t ws_bytes,
                                  kw_stream_t stream) {
-  if (!qkv || !k_cache || !v_cache || !cur_len || !out || B <= 0 || q_len <= 0 || H <= 0 || t_max <= 0 || t_max > 512)
-    return kw_set_error_msg(KW_EINVAL, "kw_self_attn_step: invalid arguments (t_max <= 512)");
-  if (hd != HD) return kw_set_error_msg(KW_EUNSUPPORTED, "kw_self_attn_step: head_dim must be 64");
+  if (const int rc = self_attn_check("kw_self_attn_step", false, dtype, qkv, B, q_len, H, hd, k_cache, v_cache, t_max,
+                                     cur_len, nullptr, bp, bp_stride, out, workspace, ws_bytes))
+    return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (bp && (q_len != 1 || bp_stride < t_max))
-    return kw_set_error_msg(KW_EINVAL, "kw_self_attn_step: a slot table needs q_len == 1 and bp_stride >= t_max");
   if (q_len == 1) {
-    if (!workspace || ws_bytes < kw_self_attn_workspace(B, H, t_max))
-      return kw_set_error_msg(KW_EINVAL, "kw_self_attn_step: needs a zero-filled workspace of kw_self_attn_workspace()");
-    float* part = (float*)workspace;
-    int* cnt = (int*)((char*)workspace + (size_t)(B * H) * 2 * (HD + 2) * sizeof(float));
+    const SelfLayout W(B, H);
     dim3 grid((unsigned)(B * H), (unsigned)((t_max + 255) / 256));
     if (dtype == KW_DT_BF16)
       hipLaunchKernelGGL((bp ? self_attn_step1<bf16_t, true> : self_attn_step1<bf16_t, false>), grid, dim3(256), 0, s,
                          (const bf16_t*)qkv, (int)H, (bf16_t*)k_cache, (bf16_t*)v_cache, (int)t_max, cur_len, bp,
-                         (int)bp_stride, part, cnt, (bf16_t*)out);
+                         (int)bp_stride, W.part(workspace), W.cnt(workspace), (bf16_t*)out);
     else
       hipLaunchKernelGGL((bp ? self_attn_step1<float, true> : self_attn_step1<float, false>), grid, dim3(256), 0, s,
                          (const float*)qkv, (int)H, (float*)k_cache, (float*)v_cache, (int)t_max, cur_len, bp,
-                         (int)bp_stride, part, cnt, (float*)out);
+                         (int)bp_stride, W.part(workspace), W.cnt(workspace), (float*)out);
   } else if (dtype == KW_DT_BF16) {
     hipLaunchKernelGGL(self_attn_step<bf16_t>, dim3((unsigned)(B * H)), dim3(256), 0, s, (const bf16_t*)qkv, (int)q_len,
                        (int)H, (bf16_t*)k_cache, (bf16_t*)v_cache, (int)t_max, cur_len, (bf16_t*)out);
@@ -2147,6 +2104,18 @@ static CRP cross_crp(const CrossGeo& g, const CrossLayout& L, void* ws, int64_t 
   p.H = (int)H, p.d = (int)(H * HD), p.S = (int)g.S, p.chunk = g.chunk, p.ns = g.ns;
   p.out = (bf16_t*)out;
   return p;
+}
+
+// ... and those of a launch that runs the query projection too (kw_dec_xq_cross, kw_dec_xq_cross_fp8; A: either
+// entry's argument block): the query granules, the projection workgroups and their arguments, the output layout
+template <typename A>
+static void crp_fuse_projection(CRP& p, const CrossLayout& L, const A& a) {
+  const int M = (int)a.M, d = (int)a.d;
+  p.qg = L.at<unsigned long long>(a.workspace, L.query_gran);
+  p.n_lin = d / 16;
+  p.out_t = a.ldx == KW_LD_TILED ? (M + 15) / 16 : 0;
+  p.proj = ProjArgs{reinterpret_cast<const bf16_t*>(a.x), a.ldx, M, d, d, a.ln_eps, a.ln_colsum,
+                    reinterpret_cast<const bf16x8*>(a.W), a.bias, a.scale, d, p.err + 1};
 }
 
 extern "C" int kw_cross_attn_pair_kernel(int64_t rows, int64_t S, int fused) {
@@ -2236,12 +2205,7 @@ extern "C" int kw_dec_xq_cross(const kw_dec_xq_cross_args* a, kw_stream_t stream
   if (a->ws_bytes < L.fused_end)
     return kw_set_error_msg(KW_EINVAL, "kw_dec_xq_cross: needs a zero-filled workspace of kw_dec_xq_cross_workspace()");
   CRP p = cross_crp(g, L, a->workspace, a->H, a->k, a->v, a->out);
-  const int M = (int)a->M, d = (int)a->d;
-  p.qg = L.at<unsigned long long>(a->workspace, L.query_gran);
-  p.n_lin = d / 16;
-  p.out_t = a->ldx == KW_LD_TILED ? (M + 15) / 16 : 0;
-  p.proj = ProjArgs{reinterpret_cast<const bf16_t*>(a->x), a->ldx, M, d, d, a->ln_eps, a->ln_colsum,
-                    reinterpret_cast<const bf16x8*>(a->W), a->bias, a->scale, d, p.err + 1};
+  crp_fuse_projection(p, L, *a);
   if (row_kernel_fits<true>(g))  // one pair workgroup per (row, head), chunks pipelined
     hipLaunchKernelGGL((cross_attn_row_kernel<true, ROW_NS>), dim3((unsigned)(p.n_lin + g.rows)), dim3(256), 0,
                        (hipStream_t)stream, p);
@@ -2305,12 +2269,7 @@ extern "C" int kw_dec_xq_cross_fp8(const kw_dec_xq_cross_fp8_args* a, kw_stream_
   if (a->ws_bytes < L.fused_end)
     return kw_set_error_msg(KW_EINVAL, "kw_dec_xq_cross_fp8: needs a zero-filled workspace of kw_dec_xq_cross_workspace()");
   CRP8 p = cross_crp8(cross_crp(g, L, a->workspace, a->H, a->k, a->v, a->out), a->k_scale, a->v_scale, 1);
-  const int M = (int)a->M, d = (int)a->d;
-  p.qg = L.at<unsigned long long>(a->workspace, L.query_gran);
-  p.n_lin = d / 16;
-  p.out_t = a->ldx == KW_LD_TILED ? (M + 15) / 16 : 0;
-  p.proj = ProjArgs{reinterpret_cast<const bf16_t*>(a->x), a->ldx, M, d, d, a->ln_eps, a->ln_colsum,
-                    reinterpret_cast<const bf16x8*>(a->W), a->bias, a->scale, d, p.err + 1};
+  crp_fuse_projection(p, L, *a);
   hipLaunchKernelGGL((cross_attn_row_fp8_kernel<true, ROW_NS>), dim3((unsigned)(p.n_lin + g.rows)), dim3(256), 0,
                      (hipStream_t)stream, p);
   KW_CHECK_LAUNCH();
@@ -2323,12 +2282,11 @@ static void launch_self_attn_masked(const void* qkv, int64_t B, int64_t q_len, i
                                     int64_t t_max, const int32_t* cur_len, const int32_t* key_start, const int32_t* bp,
                                     int64_t bp_stride, void* out, void* workspace, bool per_query, hipStream_t s) {
   if (q_len == 1) {
-    float* part = (float*)workspace;
-    int* cnt = (int*)((char*)workspace + (size_t)(B * H) * 2 * (HD + 2) * sizeof(float));
+    const SelfLayout W(B, H);
     dim3 grid((unsigned)(B * H), (unsigned)((t_max + 255) / 256));
     hipLaunchKernelGGL((bp ? self_attn_step1_masked<T, true> : self_attn_step1_masked<T, false>), grid, dim3(256), 0, s,
                        (const T*)qkv, (int)H, (T*)k_cache, (T*)v_cache, (int)t_max, cur_len, key_start, bp,
-                       (int)bp_stride, part, cnt, (T*)out);
+                       (int)bp_stride, W.part(workspace), W.cnt(workspace), (T*)out);
   } else if (sizeof(T) == 2 && !per_query) {
     hipLaunchKernelGGL(self_attn_prefill_masked_mfma, dim3((unsigned)(B * H), (unsigned)((q_len + 15) / 16)), dim3(64), 0, s,
                        (const bf16_t*)qkv, (int)q_len, (int)H, (bf16_t*)k_cache, (bf16_t*)v_cache, (int)t_max, cur_len,
@@ -2344,19 +2302,11 @@ extern "C" int kw_self_attn_step_masked(int dtype, const void* qkv, int64_t B, i
                                         void* k_cache, void* v_cache, int64_t t_max, const int32_t* cur_len,
                                         const int32_t* key_start, const int32_t* bp, int64_t bp_stride, void* out,
                                         void* workspace, size_t ws_bytes, kw_stream_t stream) {
-  if (!qkv || !k_cache || !v_cache || !cur_len || !key_start || !out || B <= 0 || q_len <= 0 || H <= 0 || t_max <= 0 ||
-      t_max > 512 || q_len > t_max)
-    return kw_set_error_msg(KW_EINVAL, "kw_self_attn_step_masked: invalid arguments (q_len <= t_max <= 512)");
-  if (hd != HD) return kw_set_error_msg(KW_EUNSUPPORTED, "kw_self_attn_step_masked: head_dim must be 64");
   const bool per_query = (dtype & KW_SELF_ATTN_PER_QUERY) != 0;
   dtype &= ~KW_SELF_ATTN_PER_QUERY;
-  if (dtype != KW_DT_BF16 && dtype != KW_DT_F32)
-    return kw_set_error_msg(KW_EUNSUPPORTED, "kw_self_attn_step_masked: dtype");
-  if (bp && (q_len != 1 || bp_stride < t_max))
-    return kw_set_error_msg(KW_EINVAL, "kw_self_attn_step_masked: a slot table needs q_len == 1 and bp_stride >= t_max");
-  if (q_len == 1 && (!workspace || ws_bytes < kw_self_attn_workspace(B, H, t_max)))
-    return kw_set_error_msg(KW_EINVAL,
-                            "kw_self_attn_step_masked: needs a zero-filled workspace of kw_self_attn_workspace()");
+  if (const int rc = self_attn_check("kw_self_attn_step_masked", true, dtype, qkv, B, q_len, H, hd, k_cache, v_cache, t_max,
+                                     cur_len, key_start, bp, bp_stride, out, workspace, ws_bytes))
+    return rc;
   hipStream_t s = (hipStream_t)stream;
   if (dtype == KW_DT_BF16)
     launch_self_attn_masked<bf16_t>(qkv, B, q_len, H, k_cache, v_cache, t_max, cur_len, key_start, bp, bp_stride, out,
