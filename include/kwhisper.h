@@ -95,7 +95,9 @@ int kw_gemm(const kw_gemm_args* args, kw_stream_t stream);
  *   RESID: h[m][n] += acc + bias (f32 residual, modeling_whisper.py:482,495,503) and hb = bf16(h), the
  *          bf16 mirror the next LayerNorm-fused linear reads.
  * W: packed by kw_pack_weight.  workspace: >= kw_dec_linear_workspace_bytes(N, K) bytes, zero-filled
- * before first use (calls leave it zeroed); one workspace may serve all calls on one stream.
+ * before first use; one workspace may serve all calls on one stream.  What must be zero is its first 16 KB, the
+ * K-split arrival counters, and every call leaves those zero again; the rest (used by K-split shapes only) is
+ * scratch for partial sums, written before it is read and left holding the last call's.
  * Results are bitwise deterministic (fixed-order reductions, no float atomics).
  *
  * Fragment-major activations: ldx == KW_LD_TILED says x is stored in the order the matrix cores take it
