@@ -158,7 +158,7 @@ template <bool REP>
 __device__ __forceinline__ void beam_logprobs_body(const kw_beam_logprobs_args& a, float penalty, int ngram) {
   __shared__ uint32_t rep_hist[REP ? REP_WORDS : 1], rep_ban[REP ? REP_WORDS : 1];
   __shared__ float shf[ST / 64];
-  __shared__ int shi[ST / 64][2];
+  __shared__ int shi[ST / 64];
   __shared__ RowState st_sh;
   if (*a.done) return;
   const int r = blockIdx.x;
@@ -173,11 +173,11 @@ __device__ __forceinline__ void beam_logprobs_body(const kw_beam_logprobs_args& 
   float m = -INFINITY;
 #pragma unroll 8
   for (int v = tid; v < V; v += ST) m = fmaxf(m, x[v]);
-  m = block_reduce_max(m, shf);
+  m = wg_max<ST>(m, shf);
   float s = 0.f;
 #pragma unroll 8
   for (int v = tid; v < V; v += ST) s += expf(x[v] - m);
-  s = block_reduce_sum(s, shf);
+  s = wg_sum<ST>(s, shf);
   const float ls = logf(s);
   if constexpr (REP) rep_bitsets<ST>(rep_hist, rep_ban, ids, L, V, penalty, ngram);
   auto lp = [&](int v) {
@@ -186,9 +186,7 @@ __device__ __forceinline__ void beam_logprobs_body(const kw_beam_logprobs_args& 
     return y;
   };
 
-  int fin = 0;
-  RowState st = row_state(ids, L, a.begin_index, a.ts_begin, a.no_ts_id, a.eos_id, a.return_timestamps,
-                          a.max_initial_ts, &fin, shi, &st_sh);
+  RowState st = history_row_state<ST>(a, ids, L, a.return_timestamps, nullptr, shi, &st_sh);
   if (st.rt) timestamp_rule(st, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, V, lp, shf);
 
   // per-thread sorted top-K of its strided slice as 64-bit (score, token) keys ordered like better() -- a -inf
@@ -249,7 +247,7 @@ __global__ __launch_bounds__(ST) void beam_lp_rep_kernel(kw_beam_logprobs_args a
   beam_logprobs_body<true>(a, penalty, ngram);
 }
 
-// ---- split-row variant: a row over BSPLIT workgroups (the one-workgroup kernel above walks a whole
+// ---- split-row variant: a row over NSPLIT workgroups (the one-workgroup kernel above walks a whole
 // vocabulary row serially in several passes; at R = 160-320 running rows that is most of a step).
 // Each slice keeps its logits in registers and publishes: the raw maximum and sum of exp (the
 // log_softmax normaliser), WhisperTimeStamp's statistics of its processed scores (as the greedy
@@ -257,7 +255,7 @@ __global__ __launch_bounds__(ST) void beam_lp_rep_kernel(kw_beam_logprobs_args a
 // log-prob tie that the raw order would split differently stays inside the candidates).  The row's
 // last arriver merges the normaliser, applies the timestamp rule, turns candidates into log-probs
 // lp = (x - m) - log(s) and keeps the k best by (lp desc, token asc).
-constexpr int BSPLIT = 8, BT_S = 512, BUNR = 16, KP = KMAX + 4, BPART = 96;
+constexpr int KP = KMAX + 4, BPART = 96;  // (NSPLIT, SPLIT_T, SUNR: processors.h)
 constexpr int REP_NORM = BPART - 2;  // REP: the row's (max, log sum exp) in its first slice record
 static_assert(9 + 4 * KP <= REP_NORM, "the slice record's published floats must leave the normaliser's two alone");
 
@@ -275,27 +273,9 @@ __device__ __forceinline__ void bl_argmax(float& best, int& bi, int& bt, float* 
   }
   __syncthreads();
   best = shf[0]; bi = shi[0]; bt = shi[1];
-  for (int w = 1; w < BT_S / 64; ++w)
+  for (int w = 1; w < SPLIT_T / 64; ++w)
     if (better(shf[w], shi[2 * w], best, bi)) { best = shf[w]; bi = shi[2 * w]; bt = shi[2 * w + 1]; }
   __syncthreads();
-}
-__device__ __forceinline__ float bl_max(float v, float* sh) {
-  v = wave_max(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = sh[0];
-  for (int i = 1; i < BT_S / 64; ++i) r = fmaxf(r, sh[i]);
-  __syncthreads();
-  return r;
-}
-__device__ __forceinline__ float bl_sum(float v, float* sh) {
-  v = wave_sum(v);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-  __syncthreads();
-  float r = 0.f;
-  for (int i = 0; i < BT_S / 64; ++i) r += sh[i];
-  __syncthreads();
-  return r;
 }
 
 // REP: the processors act on log-probs and are not shift invariant, so a slice cannot stay in raw-logit space until
@@ -318,65 +298,56 @@ __device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_
   const int K = a.k;
   const float* x = a.logits + (int64_t)r * a.V;
   const int64_t* ids = a.ids + (int64_t)r * a.ids_stride;
-  const int per = (V + BSPLIT - 1) / BSPLIT;
+  const int per = (V + NSPLIT - 1) / NSPLIT;
   const int v0 = sl * per, v1 = min(V, v0 + per);
-  float xv[BUNR];
-  bool mk[BUNR];  // SuppressTokens bytes with the logits (a mask load in the compare chain waits per element)
+  float xv[SUNR];
+  bool mk[SUNR];
+  // (kwp::split_load, spelled out: the call moved this kernel's schedule and measured +0.3 us on 31.6 us at R = 40)
 #pragma unroll
-  for (int u = 0; u < BUNR; ++u) {
-    const int v = v0 + tid + u * BT_S, vc = min(v, v1 - 1);  // unconditional (clamped) loads: no branches
+  for (int u = 0; u < SUNR; ++u) {
+    const int v = v0 + tid + u * SPLIT_T, vc = min(v, v1 - 1);  // unconditional (clamped) loads: no branches
     const float xr = x[vc];                                           // and phis between them
     const uint8_t mr = a.suppress_mask[vc];
     xv[u] = v < v1 ? xr : -INFINITY;
     mk[u] = v < v1 ? mr != 0 : true;
   }
   if constexpr (REP) {
-    const float* nrm = reinterpret_cast<const float*>(a.workspace) + (int64_t)r * BSPLIT * BPART + REP_NORM;
+    const float* nrm = reinterpret_cast<const float*>(a.workspace) + (int64_t)r * NSPLIT * BPART + REP_NORM;
     const float m = nrm[0], ls = nrm[1];  // (beam_rep_norm_kernel, the launch before this one)
-    rep_bitsets<BT_S>(rep_hist, rep_ban, ids, L, V, penalty, ngram);
+    rep_bitsets<SPLIT_T>(rep_hist, rep_ban, ids, L, V, penalty, ngram);
 #pragma unroll
-    for (int u = 0; u < BUNR; ++u) {
-      const int v = v0 + tid + u * BT_S;
+    for (int u = 0; u < SUNR; ++u) {
+      const int v = v0 + tid + u * SPLIT_T;
       if (v < v1) xv[u] = rep_apply(rep_hist, rep_ban, penalty, v, (xv[u] - m) - ls);
     }
   }
-  // row state from the history (as kwp::row_state, BT_S threads): the last timestamp position travels with
-  // its token in one 64-bit key (no dependent reload), the last two tokens are read up front
+  // row state from the history (kwp::history_row_state's, with no dependent load): the last timestamp position
+  // travels with its token in one 64-bit key, the last two tokens are read up front
   const int n_hist = L - a.begin_index;
   const int64_t tok_l1 = n_hist >= 1 ? ids[L - 1] : 0, tok_l2 = n_hist >= 2 ? ids[L - 2] : 0;
   uint64_t lkey = 0;  // ((position + 1) << 32) | token of the row's last timestamp
-  for (int p = a.begin_index + tid; p < L; p += BT_S) {
+  for (int p = a.begin_index + tid; p < L; p += SPLIT_T) {
     const int64_t t = ids[p];
     if (t >= a.ts_begin) lkey = ((uint64_t)(uint32_t)(p + 1) << 32) | (uint32_t)t;
   }
   lkey = wave_max_u64(lkey);
-  __shared__ uint64_t lkeys[BT_S / 64];
+  __shared__ uint64_t lkeys[SPLIT_T / 64];
   if ((tid & 63) == 0) lkeys[tid >> 6] = lkey;
   __syncthreads();
   if (tid == 0) {
     uint64_t lk = lkeys[0];
-    for (int i = 1; i < BT_S / 64; ++i) lk = lkeys[i] > lk ? lkeys[i] : lk;
-    const int lp = (int)(lk >> 32) - 1;
-    const int lp_tok = (int)(uint32_t)lk;
-    RowState st;
-    st.L = L; st.begin = a.begin_index; st.ts_begin = a.ts_begin; st.no_ts = a.no_ts_id; st.eos = a.eos_id;
-    st.rt = a.return_timestamps; st.max_init = a.max_initial_ts; st.ban_text = 0;
-    st.first_step = (L == a.begin_index);
-    st.last_ts = n_hist >= 1 && tok_l1 >= a.ts_begin;
-    st.pen_ts = n_hist < 2 || tok_l2 >= a.ts_begin;
-    st.has_stamp = lp >= 0;
-    st.stamp_lo = st.has_stamp ? ((st.last_ts && !st.pen_ts) ? lp_tok : lp_tok + 1) : 0;
-    st_sh = st;
+    for (int i = 1; i < SPLIT_T / 64; ++i) lk = lkeys[i] > lk ? lkeys[i] : lk;
+    st_sh = make_row_state(a, L, a.return_timestamps, tok_l1, tok_l2, (int)(lk >> 32) - 1, (int)(uint32_t)lk);
   }
   __syncthreads();
   const RowState st = st_sh;
   // processed scores (raw-logit space; every processor is shift invariant) and their statistics
-  float sv[BUNR];
+  float sv[SUNR];
   float mr = -INFINITY, mt = -INFINITY, ms = -INFINITY;
   int it = 0x7fffffff, is = 0x7fffffff;
 #pragma unroll
-  for (int u = 0; u < BUNR; ++u) {
-    const int v = v0 + tid + u * BT_S;
+  for (int u = 0; u < SUNR; ++u) {
+    const int v = v0 + tid + u * SPLIT_T;
     mr = fmaxf(mr, xv[u]);
     sv[u] = v < v1 ? process_m(st, mk[u], a.begin_suppress, a.n_begin_suppress, v, xv[u]) : -INFINITY;
     if (v < v1) {
@@ -387,9 +358,9 @@ __device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_
   }
   // one workgroup round for the three maxima (the raw maximum of the log_softmax normaliser; the best
   // text and timestamp scores as 64-bit keys), one for the three sums
-  __shared__ float rmx[BT_S / 64];
-  __shared__ uint64_t rkt[BT_S / 64], rks[BT_S / 64];
-  __shared__ float rsum[3][BT_S / 64];
+  __shared__ float rmx[SPLIT_T / 64];
+  __shared__ uint64_t rkt[SPLIT_T / 64], rks[SPLIT_T / 64];
+  __shared__ float rsum[3][SPLIT_T / 64];
   {
     mr = wave_max(mr);
     uint64_t kt = 0, ks = 0;
@@ -402,7 +373,7 @@ __device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_
     mr = rmx[0];
     kt = rkt[0];
     ks = rks[0];
-    for (int w = 1; w < BT_S / 64; ++w) {
+    for (int w = 1; w < SPLIT_T / 64; ++w) {
       mr = fmaxf(mr, rmx[w]);
       kt = rkt[w] > kt ? rkt[w] : kt;
       ks = rks[w] > ks ? rks[w] : ks;
@@ -415,8 +386,8 @@ __device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_
   float sr = 0.f, sa = 0.f, sts = 0.f, mall = -INFINITY;
   if (st.rt) mall = fmaxf(mt, ms);
 #pragma unroll
-  for (int u = 0; u < BUNR; ++u) {
-    const int v = v0 + tid + u * BT_S;
+  for (int u = 0; u < SUNR; ++u) {
+    const int v = v0 + tid + u * SPLIT_T;
     if (v < v1) {
       sr += expf(xv[u] - mr);
       if (mall > -INFINITY && sv[u] > -INFINITY) {
@@ -432,7 +403,7 @@ __device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_
     if ((tid & 63) == 0) { rsum[0][tid >> 6] = sr; rsum[1][tid >> 6] = sa; rsum[2][tid >> 6] = sts; }
     __syncthreads();
     sr = sa = sts = 0.f;
-    for (int w = 0; w < BT_S / 64; ++w) {
+    for (int w = 0; w < SPLIT_T / 64; ++w) {
       sr += rsum[0][w];
       sa += rsum[1][w];
       sts += rsum[2][w];
@@ -443,7 +414,7 @@ __device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_
   // takes the slice's kp best of the waves' 8 x kp
   const int kp = min(K + 4, KP);
   const int lane = tid & 63, wv = tid >> 6;
-  __shared__ uint64_t wck[2][BT_S / 64][KP];
+  __shared__ uint64_t wck[2][SPLIT_T / 64][KP];
   // timestamp tokens sit at the top of the vocabulary: only the slices holding some need the second list
   const int nlist = (st.rt && v1 > st.ts_begin) ? 2 : 1;
   for (int list = 0; list < nlist; ++list) {
@@ -453,8 +424,8 @@ __device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_
     auto fill = [&]() {
       c0 = c1 = c2 = 0;
 #pragma unroll
-      for (int u = 0; u < BUNR; ++u) {
-        const int v = v0 + tid + u * BT_S;
+      for (int u = 0; u < SUNR; ++u) {
+        const int v = v0 + tid + u * SPLIT_T;
         const uint64_t k = (v < v1 && (list == 0 || v >= st.ts_begin)) ? bkey(sv[u], v) : 0;
         if (k < floor) bins3(k, c0, c1, c2);
       }
@@ -486,7 +457,7 @@ __device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_
       }
       // the waves' 8 x kp keys (kp <= KP: at most 3 per lane), then kp rounds of a wave max
       uint64_t c0 = 0, c1 = 0, c2 = 0;
-      const int n = (BT_S / 64) * kp;
+      const int n = (SPLIT_T / 64) * kp;
 #pragma unroll
       for (int t = 0; t < 3; ++t) {
         const int e = lane + 64 * t;
@@ -507,8 +478,8 @@ __device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_
     pub[5] = __int_as_float(is); pub[6] = mall; pub[7] = sa; pub[8] = sts;
   }
   __syncthreads();
-  float* part = reinterpret_cast<float*>(a.workspace) + ((int64_t)r * BSPLIT + sl) * BPART;
-  int* rcnt = reinterpret_cast<int*>(a.workspace) + (int64_t)a.R * BSPLIT * BPART + r;
+  float* part = reinterpret_cast<float*>(a.workspace) + ((int64_t)r * NSPLIT + sl) * BPART;
+  int* rcnt = reinterpret_cast<int*>(a.workspace) + (int64_t)a.R * NSPLIT * BPART + r;
   const int npub = 9 + (st.rt ? 4 : 2) * KP;
   if (tid < npub) __hip_atomic_store(part + tid, pub[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -516,25 +487,25 @@ __device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_
   __shared__ int last;
   if (tid == 0) {
     const int prev = __hip_atomic_fetch_add(rcnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last = prev == BSPLIT - 1;
+    last = prev == NSPLIT - 1;
     if (last) __hip_atomic_store(rcnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   __syncthreads();
   if (!last) return;
   // the row's partials into LDS by the whole workgroup (one round trip), then one thread merges
-  __shared__ float allp[BSPLIT * BPART];
-  const float* row = reinterpret_cast<const float*>(a.workspace) + (int64_t)r * BSPLIT * BPART;
-  for (int i = tid; i < BSPLIT * BPART; i += BT_S)
+  __shared__ float allp[NSPLIT * BPART];
+  const float* row = reinterpret_cast<const float*>(a.workspace) + (int64_t)r * NSPLIT * BPART;
+  for (int i = tid; i < NSPLIT * BPART; i += SPLIT_T)
     allp[i] = (i % BPART) < npub ? __hip_atomic_load(row + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.f;
   __syncthreads();
   if (wv != 0) return;
-  // wave 0 merges: every lane derives the row's normaliser and the text-ban decision from the BSPLIT
+  // wave 0 merges: every lane derives the row's normaliser and the text-ban decision from the NSPLIT
   // slice records (identical on all lanes), then k rounds of a wave arg-max pick the candidates
   auto ld = [&](int q, int i) { return allp[q * BPART + i]; };
   float m = -INFINITY;
-  for (int q = 0; q < BSPLIT; ++q) m = fmaxf(m, ld(q, 0));
+  for (int q = 0; q < NSPLIT; ++q) m = fmaxf(m, ld(q, 0));
   float ssum = 0.f;
-  for (int q = 0; q < BSPLIT; ++q) {
+  for (int q = 0; q < NSPLIT; ++q) {
     const float mq = ld(q, 0);
     if (mq > -INFINITY) ssum += ld(q, 1) * expf(mq - m);
   }
@@ -543,27 +514,21 @@ __device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_
   if (st.rt) {
     float bt_ = -INFINITY, bs_ = -INFINITY, M = -INFINITY;
     int jt = 0x7fffffff, js = 0x7fffffff;
-    for (int q = 0; q < BSPLIT; ++q) {
+    for (int q = 0; q < NSPLIT; ++q) {
       if (better(ld(q, 2), __float_as_int(ld(q, 3)), bt_, jt)) { bt_ = ld(q, 2); jt = __float_as_int(ld(q, 3)); }
       if (better(ld(q, 4), __float_as_int(ld(q, 5)), bs_, js)) { bs_ = ld(q, 4); js = __float_as_int(ld(q, 5)); }
       M = fmaxf(M, ld(q, 6));
     }
     float S = 0.f, Sts = 0.f;
-    for (int q = 0; q < BSPLIT; ++q) {
+    for (int q = 0; q < NSPLIT; ++q) {
       if (ld(q, 6) > -INFINITY) S += ld(q, 7) * expf(ld(q, 6) - M);
       if (ld(q, 4) > -INFINITY) Sts += ld(q, 8) * expf(ld(q, 4) - bs_);
     }
-    if (M > -INFINITY) {
-      const float lse = logf(S);
-      const float lp_text_max = (bt_ - M) - lse;
-      const float lp_ts_max = (bs_ - M) - lse;
-      const float ts_lse = lp_ts_max > -INFINITY ? lp_ts_max + logf(Sts) : -INFINITY;
-      ban = ts_lse > lp_text_max;
-    }
+    if (M > -INFINITY) ban = mass_rule_ban(bt_, bs_, M, S, Sts);
   }
-  // candidates of the chosen list as log-probs, three per lane (BSPLIT x kp <= 192)
+  // candidates of the chosen list as log-probs, three per lane (NSPLIT x kp <= 192)
   const int base = 9 + (ban ? 2 * KP : 0);
-  const int n = BSPLIT * kp;
+  const int n = NSPLIT * kp;
   float c[3];
   int ci3[3];
 #pragma unroll
@@ -619,10 +584,10 @@ __device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_
   }
 }
 
-__global__ __launch_bounds__(BT_S) void beam_logprobs_split_kernel(kw_beam_logprobs_args a) {
+__global__ __launch_bounds__(SPLIT_T) void beam_logprobs_split_kernel(kw_beam_logprobs_args a) {
   beam_logprobs_split_body<false>(a, 1.0f, 0);
 }
-__global__ __launch_bounds__(BT_S) void beam_lp_rep_split_kernel(kw_beam_logprobs_args a, float penalty, int ngram) {
+__global__ __launch_bounds__(SPLIT_T) void beam_lp_rep_split_kernel(kw_beam_logprobs_args a, float penalty, int ngram) {
   beam_logprobs_split_body<true>(a, penalty, ngram);
 }
 // the row's log_softmax normaliser, as beam_logprobs_body takes it, for the launch above
@@ -634,13 +599,13 @@ __global__ __launch_bounds__(ST) void beam_rep_norm_kernel(kw_beam_logprobs_args
   float m = -INFINITY;
 #pragma unroll 8
   for (int v = tid; v < V; v += ST) m = fmaxf(m, x[v]);
-  m = block_reduce_max(m, shf);
+  m = wg_max<ST>(m, shf);
   float s = 0.f;
 #pragma unroll 8
   for (int v = tid; v < V; v += ST) s += expf(x[v] - m);
-  s = block_reduce_sum(s, shf);
+  s = wg_sum<ST>(s, shf);
   if (tid == 0) {
-    float* nrm = reinterpret_cast<float*>(a.workspace) + (int64_t)r * BSPLIT * BPART + REP_NORM;
+    float* nrm = reinterpret_cast<float*>(a.workspace) + (int64_t)r * NSPLIT * BPART + REP_NORM;
     nrm[0] = m;
     nrm[1] = logf(s);
   }
@@ -912,15 +877,15 @@ bool beam_select_args_ok(const kw_beam_select_args* a) {
 }  // namespace
 
 extern "C" size_t kw_beam_logprobs_workspace(int64_t R) {
-  return (size_t)R * BSPLIT * BPART * sizeof(float) + (size_t)R * sizeof(int);
+  return (size_t)R * NSPLIT * BPART * sizeof(float) + (size_t)R * sizeof(int);
 }
 
 extern "C" int kw_beam_logprobs(const kw_beam_logprobs_args* a, kw_stream_t stream) {
   if (!a || !a->logits || !a->suppress_mask || !a->ids || !a->cur_len || !a->cand_val || !a->cand_idx || !a->done ||
       a->R <= 0 || a->V <= 0 || a->k < 1 || a->k > KMAX || (a->n_begin_suppress > 0 && !a->begin_suppress))
     return kw_set_error_msg(KW_EINVAL, "kw_beam_logprobs: invalid arguments (k <= 16)");
-  if (a->workspace && a->ws_bytes >= kw_beam_logprobs_workspace(a->R) && a->V <= (int64_t)BSPLIT * BT_S * BUNR)
-    hipLaunchKernelGGL(beam_logprobs_split_kernel, dim3((unsigned)a->R, BSPLIT), dim3(BT_S), 0, (hipStream_t)stream, *a);
+  if (a->workspace && a->ws_bytes >= kw_beam_logprobs_workspace(a->R) && a->V <= (int64_t)NSPLIT * SPLIT_T * SUNR)
+    hipLaunchKernelGGL(beam_logprobs_split_kernel, dim3((unsigned)a->R, NSPLIT), dim3(SPLIT_T), 0, (hipStream_t)stream, *a);
   else
     hipLaunchKernelGGL(beam_logprobs_kernel, dim3((unsigned)a->R), dim3(ST), 0, (hipStream_t)stream, *a);
   KW_CHECK_LAUNCH();
@@ -935,9 +900,9 @@ extern "C" int kw_beam_logprobs_rep(const kw_beam_logprobs_args* a, float penalt
                             "kw_beam_logprobs_rep: invalid arguments (k <= 16, penalty > 0 and finite, ngram >= 0)");
   if (a->V > REP_VMAX) return kw_set_error_msg(KW_EUNSUPPORTED, "kw_beam_logprobs_rep: V > 65536");
   if (penalty == 1.0f && ngram == 0) return kw_beam_logprobs(a, stream);  // both off: that very launch
-  if (a->workspace && a->ws_bytes >= kw_beam_logprobs_workspace(a->R) && a->V <= (int64_t)BSPLIT * BT_S * BUNR) {
+  if (a->workspace && a->ws_bytes >= kw_beam_logprobs_workspace(a->R) && a->V <= (int64_t)NSPLIT * SPLIT_T * SUNR) {
     hipLaunchKernelGGL(beam_rep_norm_kernel, dim3((unsigned)a->R), dim3(ST), 0, (hipStream_t)stream, *a);
-    hipLaunchKernelGGL(beam_lp_rep_split_kernel, dim3((unsigned)a->R, BSPLIT), dim3(BT_S), 0, (hipStream_t)stream, *a,
+    hipLaunchKernelGGL(beam_lp_rep_split_kernel, dim3((unsigned)a->R, NSPLIT), dim3(SPLIT_T), 0, (hipStream_t)stream, *a,
                        penalty, (int)ngram);
   } else {
     hipLaunchKernelGGL(beam_lp_rep_kernel, dim3((unsigned)a->R), dim3(ST), 0, (hipStream_t)stream, *a, penalty,

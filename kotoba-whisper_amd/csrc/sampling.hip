@@ -7,9 +7,11 @@
 // -> finished rows emit pad (:2929) -> MaxLength / EOS stopping (stopping_criteria.py:75-77).
 // The WhisperTimeStamp per-row state (last / penultimate token, last timestamp, finished flag) is
 // derived from the row's own id history each step, exactly as the reference re-derives it from
-// input_ids.  With timestamps: one 1024-thread workgroup per row; the processed row is recomputed on
+// input_ids.  Without a workspace: one 1024-thread workgroup per row; the processed row is recomputed on
 // the fly in each of the four L2-resident passes (max, sum, timestamp log-sum-exp, argmax) instead of
-// materialised.  Without: greedy_step_split_kernel (a row over NSPLIT workgroups).
+// materialised.  With one: a row over NSPLIT workgroups (greedy_step_split_kernel, greedy_step_split_ts_kernel).
+// Every step these kernels share with each other, with kw_sample_step below and with kw_spec_accept (the row
+// state, the slice load and walk, the reductions, the arrival count, the end of a step) is a function of processors.h.
 #include <math.h>
 
 #include "processors.h"
@@ -20,7 +22,7 @@ using namespace kwp;
 
 __global__ __launch_bounds__(ST) void greedy_step_kernel(kw_sampler_args a) {
   __shared__ float shf[ST / 64];
-  __shared__ int shi[ST / 64][2];
+  __shared__ int shi[ST / 64];
   __shared__ RowState st_sh;
   const int b = blockIdx.x;
   const int tid = threadIdx.x;
@@ -31,8 +33,7 @@ __global__ __launch_bounds__(ST) void greedy_step_kernel(kw_sampler_args a) {
 
   // ---- history: finished flag and the WhisperTimeStamp row state --------------------------------
   int fin = 0;
-  RowState st = row_state(ids, L, a.begin_index, a.ts_begin, a.no_ts_id, a.eos_id, a.return_timestamps,
-                          a.max_initial_ts, &fin, shi, &st_sh);
+  RowState st = history_row_state<ST>(a, ids, L, a.return_timestamps, &fin, shi, &st_sh);
   // ---- timestamp probability-mass rule (logits_process.py:2040-2045) ---------------------------
   if (st.rt) timestamp_rule(st, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, V, [&](int v) { return x[v]; }, shf);
 
@@ -59,36 +60,23 @@ __global__ __launch_bounds__(ST) void greedy_step_kernel(kw_sampler_args a) {
       }
     }
   }
+  // (wg_argmax<ST>, spelled out with thread 0 alone merging the waves: with the call here hipcc's gfx950 code lost
+  // the first unrolled element's logit on the timestamp path above, and test_greedy_step_vs_oracle caught it)
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float ob = __shfl_xor(best, o, 64);
     const int oi = __shfl_xor(bi, o, 64);
     if (ob > best || (ob == best && oi < bi)) { best = ob; bi = oi; }
   }
-  if ((tid & 63) == 0) { shf[tid >> 6] = best; shi[tid >> 6][1] = bi; }
+  if ((tid & 63) == 0) { shf[tid >> 6] = best; shi[tid >> 6] = bi; }
   __syncthreads();
   if (tid == 0) {
     float bb = shf[0];
-    int ii = shi[0][1];
+    int ii = shi[0];
     for (int i = 1; i < ST / 64; ++i) {
-      if (shf[i] > bb || (shf[i] == bb && shi[i][1] < ii)) { bb = shf[i]; ii = shi[i][1]; }
+      if (shf[i] > bb || (shf[i] == bb && shi[i] < ii)) { bb = shf[i]; ii = shi[i]; }
     }
-    if (ii == 0x7fffffff) ii = 0;  // all -inf (cannot happen with a sane config): torch.argmax -> 0
-    const int64_t tok = fin ? (int64_t)a.pad_id : (int64_t)ii;
-    a.ids[(int64_t)b * a.ids_stride + L] = tok;
-    const int done = fin || tok == a.eos_id || (L + 1) >= a.max_length;
-    a.unfinished[b] = done ? 0 : 1;
-    __threadfence();
-    const int prev = atomicAdd(a.counter, 1);
-    if (prev == (int)a.B - 1) {
-      __threadfence();
-      int n = 0;
-      for (int i = 0; i < (int)a.B; ++i) n += __hip_atomic_load(a.unfinished + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      *a.n_unfinished = n;
-      *a.counter = 0;
-      *a.cur_len = L + 1;
-      __threadfence();
-    }
+    finish_row(a, b, L, fin, ii);
   }
 }
 
@@ -96,9 +84,7 @@ __global__ __launch_bounds__(ST) void greedy_step_kernel(kw_sampler_args a) {
 // 512-thread workgroup each (16 loads in flight per thread: one memory round trip per slice instead of
 // a serial walk over the row); each slice publishes its (max, first index, finished flag) write-through,
 // and the last of all B x NSPLIT workgroups to arrive combines every row's slices in slice order (first
-// index on ties, as torch.argmax) and finishes the step exactly as greedy_step_kernel does.
-// (SPLIT_T, NSPLIT, SUNR, PART: processors.h, with the timestamp-mode slice statistics and merge kw_spec_accept shares)
-
+// index on ties, as torch.argmax) and finishes the step as finish_row does, for every row at once.
 __global__ __launch_bounds__(SPLIT_T) void greedy_step_split_kernel(kw_sampler_args a) {
   __shared__ float shf[SPLIT_T / 64];
   __shared__ int shi[SPLIT_T / 64];
@@ -115,31 +101,14 @@ __global__ __launch_bounds__(SPLIT_T) void greedy_step_split_kernel(kw_sampler_a
   // below cost one round trip per element; the history scan's loop waits on every load it has issued)
   float xv[SUNR];
   bool mk[SUNR];
-#pragma unroll
-  for (int u = 0; u < SUNR; ++u) {
-    const int v = v0 + tid + u * SPLIT_T, vc = min(v, v1 - 1);  // unconditional (clamped) loads: no branches
-    const float xr = x[vc];                                           // and phis between them
-    const uint8_t mr = a.suppress_mask[vc];
-    xv[u] = v < v1 ? xr : -INFINITY;
-    mk[u] = v < v1 ? mr != 0 : true;
-  }
+  split_load(x, a.suppress_mask, v0, v1, xv, mk);
   // a row is finished once it emitted EOS (stopping_criteria.py:75-77): one id per thread, in parallel
   // (the row's last arriver needs it; a serial walk there would pay one load latency per position)
   int fin = 0;
   for (int p = a.begin_index + tid; p < L; p += SPLIT_T) fin |= ids[p] == a.eos_id;
   float best = -INFINITY;
   int bi = 0x7fffffff;
-  for (int vb = v0; vb < v1; vb += SPLIT_T * SUNR) {  // one round for V <= NSPLIT * 8192
-    if (vb != v0) {
-#pragma unroll
-      for (int u = 0; u < SUNR; ++u) {
-        const int v = vb + tid + u * SPLIT_T, vc = min(v, v1 - 1);  // unconditional (clamped) loads: no branches
-        const float xr = x[vc];                                           // and phis between them
-        const uint8_t mr = a.suppress_mask[vc];
-        xv[u] = v < v1 ? xr : -INFINITY;
-        mk[u] = v < v1 ? mr != 0 : true;
-      }
-    }
+  for (int vb = v0; vb < v1;) {  // one round for V <= NSPLIT * 8192
 #pragma unroll
     for (int u = 0; u < SUNR; ++u) {
       const int v = vb + tid + u * SPLIT_T;
@@ -151,7 +120,11 @@ __global__ __launch_bounds__(SPLIT_T) void greedy_step_split_kernel(kw_sampler_a
         if (s > best || (s == best && v < bi)) { best = s; bi = v; }
       }
     }
+    vb += SPLIT_T * SUNR;
+    if (vb < v1) split_load(x, a.suppress_mask, vb, v1, xv, mk);  // beyond that the window is reloaded, not walked as a tail
   }
+  // (wg_argmax<SPLIT_T>, spelled out: thread 0 alone merges the waves, behind the barrier the finished flag needs
+  // anyway -- the call's two barriers more measured +0.18 us on 15.25 us at B = 32, V = 51866)
 #pragma unroll
   for (int o = 32; o > 0; o >>= 1) {
     const float ob = __shfl_xor(best, o, 64);
@@ -172,9 +145,7 @@ __global__ __launch_bounds__(SPLIT_T) void greedy_step_split_kernel(kw_sampler_a
     __hip_atomic_store(part, best, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(reinterpret_cast<int*>(part) + 1, bi, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(reinterpret_cast<int*>(part) + 2, fin, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int prev = __hip_atomic_fetch_add(a.counter, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last_sh = prev == (int)a.B * NSPLIT - 1;
+    last_sh = arrive_last(a.counter, (int)a.B * NSPLIT);
   }
   __syncthreads();
   if (!last_sh) return;
@@ -233,25 +204,8 @@ __global__ __launch_bounds__(SPLIT_T) void greedy_step_split_ts_kernel(kw_sample
   float xv[SUNR];
   bool mk[SUNR];
   split_load(x, a.suppress_mask, v0, v1, xv, mk);  // in flight while the history is scanned
-  // ---- row state from the id history (as kwp::row_state, 512 threads) ----
-  int fin = 0, lsp = -1;
-  for (int p = a.begin_index + tid; p < L; p += SPLIT_T) {
-    const int64_t t = ids[p];
-    fin |= t == a.eos_id;
-    if (t >= a.ts_begin) lsp = max(lsp, p);
-  }
-  fin = __syncthreads_or(fin);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) lsp = max(lsp, __shfl_xor(lsp, o, 64));
-  if ((tid & 63) == 0) shi[tid >> 6] = lsp;
-  __syncthreads();
-  if (tid == 0) {
-    int lp = shi[0];
-    for (int i = 1; i < SPLIT_T / 64; ++i) lp = max(lp, shi[i]);
-    st_sh = split_row_state(ids, L, lp, a.begin_index, a.ts_begin, a.no_ts_id, a.eos_id, 1, a.max_initial_ts);
-  }
-  __syncthreads();
-  const RowState st = st_sh;
+  int fin = 0;
+  const RowState st = history_row_state<SPLIT_T>(a, ids, L, 1, &fin, shi, &st_sh);
   // ---- the slice's statistics over its processed scores, published; the row's last arriver merges ----
   float vals[7];
   split_slice_stats(st, x, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, v0, v1, xv, mk, shf, shi, vals);
@@ -259,34 +213,17 @@ __global__ __launch_bounds__(SPLIT_T) void greedy_step_split_ts_kernel(kw_sample
   float* part = reinterpret_cast<float*>(a.workspace) + ((int64_t)b * NSPLIT + sl) * PART;
   int* rcnt = reinterpret_cast<int*>(a.workspace) + (int64_t)a.B * NSPLIT * PART + b;
   split_publish(part, vals);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const int prev = __hip_atomic_fetch_add(rcnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (prev != NSPLIT - 1) return;
+  if (!arrive_last(rcnt, NSPLIT)) return;
   __hip_atomic_store(rcnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  int ii = split_merge_token(reinterpret_cast<const float*>(a.workspace) + (int64_t)b * NSPLIT * PART, 1);
-  if (ii == 0x7fffffff) ii = 0;
-  const int64_t tok = fin ? (int64_t)a.pad_id : (int64_t)ii;
-  a.ids[(int64_t)b * a.ids_stride + L] = tok;
-  const int done = fin || tok == a.eos_id || (L + 1) >= a.max_length;
-  a.unfinished[b] = done ? 0 : 1;
-  __threadfence();
-  const int prev2 = atomicAdd(a.counter, 1);
-  if (prev2 == (int)a.B - 1) {
-    __threadfence();
-    int n = 0;
-    for (int i = 0; i < (int)a.B; ++i) n += __hip_atomic_load(a.unfinished + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *a.n_unfinished = n;
-    *a.counter = 0;
-    *a.cur_len = L + 1;
-    __threadfence();
-  }
+  finish_row(a, b, L, fin, split_merge_token(reinterpret_cast<const float*>(a.workspace) + (int64_t)b * NSPLIT * PART, 1));
 }
 
 // ---- sampling step with running log-probabilities (kw_sample_step; include/kwhisper.h has the contract) ----
-// greedy_step_split_ts_kernel's split, publish and last-arriver merge, in both timestamp modes, with two additions:
-// every slice also keeps the best PERTURBED score s * inv_T + g of its text and of its timestamp tokens (the mass
-// rule needs the whole row before text may be chosen, so the merge decides between them), and the row's merge adds
-// the chosen token's log-probability under the processed, un-warped scores to the row's running sum.
+// greedy_step_split_ts_kernel's split, publish and last-arriver merge, in both timestamp modes, with two additions,
+// which are all this kernel states for itself: every slice also keeps the best PERTURBED score s * inv_T + g of its
+// text and of its timestamp tokens (the mass rule needs the whole row before text may be chosen, so the merge decides
+// between them), and the row's merge adds the chosen token's log-probability under the processed, un-warped scores
+// to the row's running sum.
 
 // Philox4x32-10 (Salmon et al., SC'11): word `w` of the block of counter c, key k
 __device__ __forceinline__ uint32_t philox4x32_10(uint32_t c0, uint32_t c1, uint32_t c2, uint32_t c3, uint32_t k0,
@@ -338,14 +275,7 @@ __global__ __launch_bounds__(SPLIT_T) void sample_step_kernel(kw_sample_args a) 
   const int v0 = sl * per, v1 = min(V, v0 + per);
   float xv[SUNR];
   bool mk[SUNR];
-#pragma unroll
-  for (int u = 0; u < SUNR; ++u) {  // the slice's logits and mask bytes in flight while the history is scanned
-    const int v = v0 + tid + u * SPLIT_T, vc = min(v, v1 - 1);  // unconditional (clamped) loads: no branches
-    const float xr = x[vc];                                           // and phis between them
-    const uint8_t mr = a.suppress_mask[vc];
-    xv[u] = v < v1 ? xr : -INFINITY;
-    mk[u] = v < v1 ? mr != 0 : true;
-  }
+  split_load(x, a.suppress_mask, v0, v1, xv, mk);  // in flight while the history is scanned
   SampleRng rng;
   {
     const uint64_t seed = *a.seed;
@@ -355,105 +285,47 @@ __global__ __launch_bounds__(SPLIT_T) void sample_step_kernel(kw_sample_args a) 
     rng.on = rng.inv_t != 0.f;
     rng.out = a.noise_out ? a.noise_out + (int64_t)b * a.V : nullptr;
   }
-  // ---- row state from the id history (as greedy_step_split_ts_kernel); an inactive row is finished ----
-  int fin = a.active ? a.active[b] == 0 : 0, lsp = -1;
-  for (int p = a.begin_index + tid; p < L; p += SPLIT_T) {
-    const int64_t t = ids[p];
-    fin |= t == a.eos_id;
-    if (t >= a.ts_begin) lsp = max(lsp, p);
-  }
-  fin = __syncthreads_or(fin);
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) lsp = max(lsp, __shfl_xor(lsp, o, 64));
-  if ((tid & 63) == 0) shi[tid >> 6] = lsp;
-  __syncthreads();
-  if (tid == 0) {
-    int lp = shi[0];
-    for (int i = 1; i < SPLIT_T / 64; ++i) lp = max(lp, shi[i]);
-    RowState st;
-    st.L = L; st.begin = a.begin_index; st.ts_begin = a.ts_begin; st.no_ts = a.no_ts_id; st.eos = a.eos_id;
-    st.rt = a.return_timestamps != 0; st.max_init = a.max_initial_ts; st.ban_text = 0;
-    const int n = L - a.begin_index;
-    st.first_step = (L == a.begin_index);
-    st.last_ts = n >= 1 && ids[L - 1] >= a.ts_begin;
-    st.pen_ts = n < 2 || ids[L - 2] >= a.ts_begin;
-    st.has_stamp = lp >= 0;
-    st.stamp_lo = st.has_stamp ? ((st.last_ts && !st.pen_ts) ? (int)ids[lp] : (int)ids[lp] + 1) : 0;
-    st_sh = st;
-  }
-  __syncthreads();
-  const RowState st = st_sh;
-  // ---- processed scores of the slice (held in registers): plain and perturbed maxima of both classes ----
+  int fin = a.active ? a.active[b] == 0 : 0;  // an inactive row is finished
+  const RowState st = history_row_state<SPLIT_T>(a, ids, L, a.return_timestamps != 0, &fin, shi, &st_sh);
+  // ---- the slice's statistics: plain maxima and best perturbed scores of both classes, then the two sums ----
   float sv[SUNR];
-  float mt = -INFINITY, ms = -INFINITY, pt = -INFINITY, ps = -INFINITY;
-  int jt = 0x7fffffff, js = 0x7fffffff;
-#pragma unroll
-  for (int u = 0; u < SUNR; ++u) {
-    const int v = v0 + tid + u * SPLIT_T;
-    sv[u] = v < v1 ? process_m(st, mk[u], a.begin_suppress, a.n_begin_suppress, v, xv[u]) : -INFINITY;
-    if (v < v1) {
-      const float p = rng.perturb(v, sv[u]);
-      if (v < st.ts_begin) {
-        mt = fmaxf(mt, sv[u]);
-        if (sv[u] > -INFINITY && (p > pt || (p == pt && v < jt))) { pt = p; jt = v; }
-      } else {
-        ms = fmaxf(ms, sv[u]);
-        if (sv[u] > -INFINITY && (p > ps || (p == ps && v < js))) { ps = p; js = v; }
-      }
-    }
-  }
-  for (int vb = v0 + SPLIT_T * SUNR; vb < v1; vb += SPLIT_T) {  // V > NSPLIT * 8192 only
-    const int v = vb + tid;
-    if (v < v1) {
-      const float s = process(st, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, v, x[v]);
-      const float p = rng.perturb(v, s);
-      if (v < st.ts_begin) {
-        mt = fmaxf(mt, s);
-        if (s > -INFINITY && (p > pt || (p == pt && v < jt))) { pt = p; jt = v; }
-      } else {
-        ms = fmaxf(ms, s);
-        if (s > -INFINITY && (p > ps || (p == ps && v < js))) { ps = p; js = v; }
-      }
-    }
-  }
-  blk_argmax(pt, jt, shf, shi);
-  blk_argmax(ps, js, shf, shi);
-  mt = blk_max(mt, shf);
-  ms = blk_max(ms, shf);
+  split_process(st, a.begin_suppress, a.n_begin_suppress, v0, v1, xv, mk, sv);
+  struct Acc {
+    float mt = -INFINITY, ms = -INFINITY;  // plain maxima
+    SliceBest p;                           // best perturbed scores among the scores that are not -inf
+  };
+  Acc m = split_fold(st, x, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, v0, v1, sv, Acc(),
+                     [&](Acc m, int v, float s) {
+                       const float p = rng.perturb(v, s);
+                       const bool text = v < st.ts_begin;
+                       if (text) m.mt = fmaxf(m.mt, s); else m.ms = fmaxf(m.ms, s);
+                       if (s > -INFINITY) m.p = slice_take(m.p, text, p, v);
+                       return m;
+                     });
+  float pt = m.p.mt, ps = m.p.ms;
+  int jt = m.p.it, js = m.p.is;
+  wg_argmax<SPLIT_T>(pt, jt, shf, shi);
+  wg_argmax<SPLIT_T>(ps, js, shf, shi);
+  const float mt = wg_max<SPLIT_T>(m.mt, shf), ms = wg_max<SPLIT_T>(m.ms, shf);
   const float mall = fmaxf(mt, ms);
-  float sa = 0.f, sts = 0.f;
-  if (mall > -INFINITY) {
-#pragma unroll
-    for (int u = 0; u < SUNR; ++u) {
-      const int v = v0 + tid + u * SPLIT_T;
-      if (v < v1 && sv[u] > -INFINITY) {
-        sa += expf(sv[u] - mall);
-        if (v >= st.ts_begin) sts += expf(sv[u] - ms);
+  struct Sums { float sa = 0.f, sts = 0.f; } z;
+  if (mall > -INFINITY)
+    z = split_fold(st, x, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, v0, v1, sv, z, [&](Sums z, int v, float s) {
+      if (s > -INFINITY) {
+        z.sa += expf(s - mall);
+        if (v >= st.ts_begin) z.sts += expf(s - ms);
       }
-    }
-    for (int vb = v0 + SPLIT_T * SUNR; vb < v1; vb += SPLIT_T) {
-      const int v = vb + tid;
-      if (v < v1) {
-        const float s = process(st, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, v, x[v]);
-        if (s > -INFINITY) {
-          sa += expf(s - mall);
-          if (v >= st.ts_begin) sts += expf(s - ms);
-        }
-      }
-    }
-  }
-  sa = blk_sum(sa, shf);
-  sts = blk_sum(sts, shf);
+      return z;
+    });
+  const float sa = wg_sum<SPLIT_T>(z.sa, shf), sts = wg_sum<SPLIT_T>(z.sts, shf);
   if (tid != 0) return;
   float* part = reinterpret_cast<float*>(a.workspace) + ((int64_t)b * NSPLIT + sl) * PART;
   int* rcnt = reinterpret_cast<int*>(a.workspace) + (int64_t)a.B * NSPLIT * PART + b;
   const float vals[8] = {mt, ms, sa, sts, pt, __int_as_float(jt), ps, __int_as_float(js)};
-#pragma unroll
-  for (int i = 0; i < 8; ++i) __hip_atomic_store(part + i, vals[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  const int prev = __hip_atomic_fetch_add(rcnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (prev != NSPLIT - 1) return;
+  split_publish(part, vals);
+  if (!arrive_last(rcnt, NSPLIT)) return;
   __hip_atomic_store(rcnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  // ---- the row's merge: the perturbed arg-max of the class the mass rule leaves, and its log-probability ----
   const float* row = reinterpret_cast<const float*>(a.workspace) + (int64_t)b * NSPLIT * PART;
   float P[NSPLIT][8];
 #pragma unroll
@@ -477,42 +349,21 @@ __global__ __launch_bounds__(SPLIT_T) void sample_step_kernel(kw_sample_args a) 
     if (P[q][1] > -INFINITY) Sts += P[q][3] * expf(P[q][1] - Mts);
   }
   int ban = 0;
-  if (st.rt && M > -INFINITY) {  // the mass rule, on the un-warped scores (as greedy_step_split_ts_kernel)
-    const float lse = logf(S);
-    const float lp_text_max = (bt - M) - lse;
-    const float lp_ts_max = (Mts - M) - lse;
-    const float ts_lse = lp_ts_max > -INFINITY ? lp_ts_max + logf(Sts) : -INFINITY;
-    ban = ts_lse > lp_text_max;
-  }
+  if (st.rt && M > -INFINITY) ban = mass_rule_ban(bt, Mts, M, S, Sts);  // on the un-warped scores
   int ii;
   if (ban) ii = ks;
   else ii = (bps > bpt) ? ks : kt;  // a tie keeps the text token (the lower index)
-  const bool none = ii == 0x7fffffff;
-  if (none) ii = 0;
-  const int64_t tok = fin ? (int64_t)a.pad_id : (int64_t)ii;
-  a.ids[(int64_t)b * a.ids_stride + L] = tok;
   if (!fin) {
     // log-probability of the token under the processed scores: with text banned they are the timestamps alone
     RowState sb = st;
     sb.ban_text = ban;
-    const float s_tok = none ? -INFINITY : process(sb, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, ii, x[ii]);
+    const float s_tok = ii == 0x7fffffff ? -INFINITY
+                                         : process(sb, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, ii, x[ii]);
     const float lp = ban ? (s_tok - Mts) - logf(Sts) : (s_tok - M) - logf(S);
     a.sum_logprob[b] += lp;
     a.n_tokens[b] += 1;
   }
-  const int done = fin || tok == a.eos_id || (L + 1) >= a.max_length;
-  a.unfinished[b] = done ? 0 : 1;
-  __threadfence();
-  const int prev2 = atomicAdd(a.counter, 1);
-  if (prev2 == (int)a.B - 1) {
-    __threadfence();
-    int n = 0;
-    for (int i = 0; i < (int)a.B; ++i) n += __hip_atomic_load(a.unfinished + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    *a.n_unfinished = n;
-    *a.counter = 0;
-    *a.cur_len = L + 1;
-    __threadfence();
-  }
+  finish_row(a, b, L, fin, ii);
 }
 
 }  // namespace

@@ -1,9 +1,10 @@
 // Speculative decoding, the accept step (kw_spec_accept; include/kwhisper.h has the contract): one launch per round,
 // for one row.  The main model's logits of the K + 1 positions L .. L + K are each turned into the token kw_greedy_step
-// would choose there -- position j over NSPLIT workgroups, each slice's statistics and the slice-ordered merge by the
-// very functions greedy_step_split_ts_kernel calls (processors.h), with the drafts ids[L, L + j) as part of the
-// history -- and the last of all (K + 1) x NSPLIT workgroups to arrive merges every position, walks the drafts (longest agreeing prefix,
-// then the correction or the bonus token) and advances the device state of both decoders.
+// would choose there -- position j over NSPLIT workgroups; the slice load, the row state, each slice's statistics, the
+// arrival count and the slice-ordered merge are the very functions greedy_step_split_ts_kernel calls (processors.h),
+// with the drafts ids[L, L + j) as part of the history -- and the last of all (K + 1) x NSPLIT workgroups to arrive
+// merges every position, walks the drafts (longest agreeing prefix, then the correction or the bonus token) and
+// advances the device state of both decoders.  What this file states for itself is that walk.
 #include <math.h>
 
 #include "processors.h"
@@ -44,31 +45,14 @@ __global__ __launch_bounds__(SPLIT_T) void spec_accept_kernel(kw_spec_accept_arg
     float xv[SUNR];
     bool mk[SUNR];
     split_load(x, a.suppress_mask, v0, v1, xv, mk);  // in flight while the history is scanned
-    // ---- row state from the id history [begin_index, L), the drafts before this position in place ----
-    int lsp = -1;
-    for (int p = a.begin_index + tid; p < L; p += SPLIT_T)
-      if (ids[p] >= a.ts_begin) lsp = max(lsp, p);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) lsp = max(lsp, __shfl_xor(lsp, o, 64));
-    if ((tid & 63) == 0) shi[tid >> 6] = lsp;
-    __syncthreads();
-    if (tid == 0) {
-      int lp = shi[0];
-      for (int i = 1; i < SPLIT_T / 64; ++i) lp = max(lp, shi[i]);
-      st_sh = split_row_state(ids, L, lp, a.begin_index, a.ts_begin, a.no_ts_id, a.eos_id, a.return_timestamps != 0,
-                              a.max_initial_ts);
-    }
-    __syncthreads();
-    const RowState st = st_sh;
+    // the row state from the id history [begin_index, L), the drafts before this position in place (no EOS flag:
+    // the accept walk below stops at an EOS itself)
+    const RowState st = history_row_state<SPLIT_T>(a, ids, L, a.return_timestamps != 0, nullptr, shi, &st_sh);
     float vals[7];
     split_slice_stats(st, x, a.suppress_mask, a.begin_suppress, a.n_begin_suppress, v0, v1, xv, mk, shf, shi, vals);
     if (tid == 0) split_publish(part, vals);
   }
-  if (tid == 0) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int prev = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    last_sh = prev == nq * NSPLIT - 1;
-  }
+  if (tid == 0) last_sh = arrive_last(cnt, nq * NSPLIT);
   __syncthreads();
   if (!last_sh) return;
   // ---- the last arriver: position q's token by thread q ----

@@ -21,6 +21,24 @@ def gen_dict(shape, pad=None) -> dict:
     return generation_constants(shape, pad_token_id=pad).to_dict()
 
 
+TAIL_V = 65545  # > 8 slices x 512 threads x 16 loads: every split kernel's walk beyond its register-held window
+
+
+def tail_case():
+    """The directed case of the split kernels' V > 65536 branch, with the large-v3 constants (timestamp_begin 50365,
+    EOS 50257): (history [3][5], logits [3][TAIL_V], tokens without timestamps, tokens with).  8 slices of 8194:
+    slices 0-6 end in a two-element tail (slice 0: ids 8192, 8193; slice 6: 57356, 57357).  Row 0's winner and row 1's
+    deciding timestamp mass lie in tail elements alone, so a walk that drops or double-counts the tail changes a token:
+    the mass rule's margin ts_lse - lp_text_max is +0.293 on row 1 (text banned) and -0.107 on row 2."""
+    hist = np.tile(np.array([[50258, 50266, 50360, 400, 500]], np.int64), (3, 1))
+    x = np.full((3, TAIL_V), -20.0, np.float32)
+    x[:, 100] = 10.0
+    x[0, 8193] = 11.0
+    x[1, 57356:57358] = 9.6
+    x[2, 57356:57358] = 9.2
+    return hist, x, [8193, 100, 100], [8193, 57356, 100]
+
+
 def oracle_features(shape, cases):
     from oracle.mel import log_mel
 

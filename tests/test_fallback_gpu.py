@@ -27,7 +27,7 @@ def _gen(V):
     if V == 1000:
         return dict(eos_token_id=880, pad_token_id=879, no_timestamps_token_id=899, max_initial_timestamp_index=50,
                     suppress_tokens=[1, 2, 7, 300, 511, 512] + list(range(881, 899)), begin_suppress_tokens=[220, 880])
-    return generation_constants({51865: TINY, 51866: LARGE_V3}[V]).to_dict()
+    return generation_constants({51865: TINY, 51866: LARGE_V3, 65545: LARGE_V3}[V]).to_dict()
 
 
 def _history(rng, B, n, gd):
@@ -146,6 +146,35 @@ def test_argmax_equals_greedy_step(B, V, rt, scenario):
         assert int(c.s["nun"].item()) == 0
     assert not c.ws.view(torch.int32)[B * 64: B * 65].any()  # per-row arrival counters back at zero
     assert c.noise is None
+
+
+@pytest.mark.parametrize("rt", [False, True])
+def test_tail_beyond_the_register_window(rt):
+    """V = 65545 (_util.tail_case: the winner of row 0 and the deciding timestamp mass of row 1 lie in the elements a
+    slice walks beyond its register-held window) at inv_temperature = 0: the stated tokens, every flag kw_greedy_step's,
+    and sum_logprob against the float64 log-softmax of the processed row within test_running_logprob's bound."""
+    from _util import TAIL_V, tail_case
+
+    hist, x, want_nots, want_ts = tail_case()
+    want = want_ts if rt else want_nots
+    B, L = 3, hist.shape[1]
+    c = Case(B, TAIL_V, rt, hist, L + 8)
+    c.set_logits(x)
+    c.sample()
+    c.greedy()
+    torch.cuda.synchronize()
+    for k in ("ids", "unf", "nun", "cur", "cnt"):
+        assert torch.equal(c.s[k], c.g[k]), k
+    assert c.s["ids"][:, L].tolist() == want and c.s["unf"].tolist() == [1, 1, 1]
+    assert (int(c.s["nun"].item()), int(c.s["cur"].item())) == (B, L + 1) and c.n_tok.tolist() == [1, 1, 1]
+    s = c.processed(hist, x)
+    rows = np.arange(B)
+    want64 = R.log_softmax64(s)[rows, want]
+    want32 = torch.log_softmax(torch.from_numpy(s), -1).numpy()[rows, want]
+    err_gpu = float(np.abs(c.sum_lp.cpu().numpy() - want64).max())
+    err_torch = float(np.abs(want32 - want64).max())
+    print(f"sum_logprob V={TAIL_V} rt={rt}: err gpu {err_gpu:.3e} torch fp32 {err_torch:.3e}")
+    assert err_gpu <= max(4 * err_torch, 1e-6)
 
 
 # ---- running log-probability ----------------------------------------------------------------------------------------

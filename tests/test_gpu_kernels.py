@@ -600,8 +600,47 @@ def test_greedy_step_vs_oracle(rt, n_hist):
 
 
 @pytest.mark.parametrize("rt", [False, True])
+def test_greedy_step_tail_beyond_the_register_window(rt):
+    """V = 65545 > 8 x 512 x 16: the split kernels' walk beyond the window a slice holds in registers (_util.tail_case:
+    the winner of row 0 and the deciding timestamp mass of row 1 are tail elements).  The stated tokens, which are the
+    pinned processors' arg-max, from the one-workgroup kernel and from the split kernel; ids and bookkeeping equal."""
+    from _util import TAIL_V, tail_case
+    from kwhisper.config import LARGE_V3, generation_constants
+    from oracle.generate import process_logits
+
+    gen = generation_constants(LARGE_V3)
+    assert (gen.timestamp_begin, gen.eos_token_id) == (50365, 50257)
+    B, P, V = 3, 3, TAIL_V
+    hist, x, want_nots, want_ts = tail_case()
+    want = want_ts if rt else want_nots
+    assert np.argmax(process_logits(hist, x, gen.to_dict(), P, rt), -1).tolist() == want
+    L = hist.shape[1]
+    sup = torch.zeros(V, dtype=torch.uint8)
+    sup[torch.tensor(gen.suppress_tokens)] = 1
+    bsup = torch.tensor(gen.begin_suppress_tokens, dtype=torch.int32, device="cuda")
+    outs = []
+    for split in (False, True):
+        ids = torch.zeros((B, 16), dtype=torch.int64, device="cuda")
+        ids[:, :L] = torch.from_numpy(hist)
+        cur = torch.tensor([L], dtype=torch.int32, device="cuda")
+        unf = torch.ones(B, dtype=torch.int32, device="cuda")
+        cnt = torch.zeros(1, dtype=torch.int32, device="cuda")
+        nun = torch.zeros(1, dtype=torch.int32, device="cuda")
+        ws = torch.zeros(ops.greedy_step_workspace_bytes(B) // 4 + 1, device="cuda") if split else None
+        ops.SamplerPlan(dev(x), sup.cuda(), bsup, ids, cur, unf, cnt, nun, return_timestamps=rt,
+                        ts_begin=gen.timestamp_begin, no_ts_id=gen.no_timestamps_token_id, eos_id=gen.eos_token_id,
+                        pad_id=gen.pad_token_id, max_initial_ts=gen.max_initial_timestamp_index if rt else None,
+                        max_length=16, begin_index=P, workspace=ws)()
+        torch.cuda.synchronize()
+        outs.append((ids.cpu().numpy(), int(cur.item()), unf.cpu().tolist(), int(nun.item()), int(cnt.item())))
+        assert outs[-1][0][:, L].tolist() == want, ("split" if split else "one workgroup", outs[-1][0][:, L].tolist())
+    np.testing.assert_array_equal(outs[0][0], outs[1][0])
+    assert outs[0][1:] == outs[1][1:] == (L + 1, [1, 1, 1], 3, 0)
+
+
+@pytest.mark.parametrize("rt", [False, True])
 @pytest.mark.parametrize("n_hist", [0, 1, 7])
-@pytest.mark.parametrize("B,V", [(32, 51866), (6, 51865), (3, 1000), (2, 9)])
+@pytest.mark.parametrize("B,V", [(32, 51866), (6, 51865), (3, 1000), (2, 9), (2, 65545)])
 def test_greedy_step_split_rows(rt, n_hist, B, V):
     """Split-row sampler (a row over 8 workgroups + last-arriver combine; with timestamps the probability-mass
     rule from merged per-slice log-sum-exps) == the one-workgroup kernel, token for token: ties (first

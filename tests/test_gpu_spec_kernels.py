@@ -23,7 +23,7 @@ def _gen(V):
     if V == 1000:
         return dict(eos_token_id=880, pad_token_id=879, no_timestamps_token_id=899, max_initial_timestamp_index=50,
                     suppress_tokens=[1, 2, 7, 300, 511, 512] + list(range(881, 899)), begin_suppress_tokens=[220, 880])
-    return generation_constants({51865: TINY, 51866: LARGE_V3}[V]).to_dict()
+    return generation_constants({51865: TINY, 51866: LARGE_V3, 65545: LARGE_V3}[V]).to_dict()
 
 
 def _scenario(V, K, rt, pattern, rng):
@@ -131,8 +131,8 @@ def backend(request):
 
 @pytest.mark.parametrize("pattern", PATTERNS)
 @pytest.mark.parametrize("rt", [False, True])
-@pytest.mark.parametrize("K", [1, 4, 7])
-@pytest.mark.parametrize("V", [1000, 51865, 51866])
+@pytest.mark.parametrize("V,K", [(V, K) for K in (1, 4, 7) for V in (1000, 51865, 51866)]
+                         + [(65545, 4)])  # (V > 65536: the slices' walk beyond their register-held window)
 def test_accept_equals_sequential_greedy_steps(V, K, rt, pattern, backend):
     rng = np.random.default_rng(V * 31 + K * 7 + 2 * rt + PATTERNS.index(pattern))
     gd, ids, L, x, max_length = _scenario(V, K, rt, pattern, rng)
