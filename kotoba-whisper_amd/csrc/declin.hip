@@ -39,6 +39,11 @@
 #define KW_DEC_STAMP(slot)
 #define KW_DEC_STAMP_FLUSH
 #endif
+// the launch head (tools/lab/chain_stamps.hip): 0 at the wave's first instruction, 1 where its first load can be issued
+// (the values that load's address needs are the stamp's operands)
+#ifndef KW_DEC_STAMP_HEAD
+#define KW_DEC_STAMP_HEAD(slot, ...)
+#endif
 
 namespace {
 
@@ -213,20 +218,32 @@ __device__ __forceinline__ void tile_job_epilogue(const DecP& p, const f32x4 (*r
   store_block16<EPI, TC, TH>(p, stg, v4, m0 + 16 * hj, m0 + M, nb, lane);
 }
 
+// What a wave's first loads need -- the weight and activation fragments of its k-tiles: dec_linear_kernel takes these
+// as its leading scalar parameters (in SGPRs at wave start where the kernarg preload is honoured), so the loads go out
+// before the descriptor behind them has been fetched
+struct DecHead {
+  const bf16x8* W;
+  const bf16_t* x;  // the z-chunk's first row (DecP::x of rows_window)
+  int nkt, xt;      // K / 32; DecP::xt
+  uint32_t slmul;   // kw_div_mul(K splits x waves): the k-tile range of a (split, wave) slice without a division
+};
+
 // H2: the second 16-row half of the tile exists (false: a row-split chunk of <= 16 rows -- its a1 / c1 / LayerNorm
-// statistics are never loaded or computed, which frees the registers for two workgroups per CU)
+// statistics are never loaded or computed, which frees the registers for two workgroups per CU).
+// p0: the launch's descriptor, of which this workgroup takes z-chunk zc (p0.zrows rows each)
 template <int KTM, int NCB, bool LNA, int EPI, typename TC, bool H2 = true>
-__device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int cg, const int ks, const int nw) {
+__device__ __forceinline__ void dec_linear_body(const DecHead hd, const DecP& p0, const int zc, const int ksn, const int cg,
+                                                const int ks, const int nw) {
   __shared__ f32x4 red[MAXW][NCB][2][64];
   __shared__ float rpart[MAXW][32][2];  // LayerNorm: per-wave row (sum, sum of squares)
   __shared__ float rstat[32][2];     // LayerNorm: (mean, rstd) per row
   extern __shared__ __attribute__((aligned(16))) char xs[];  // activation image (x_lds_bytes)
+  KW_DEC_STAMP_HEAD(0);
   const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);  // uniform (scalar branches)
-  const int nkt = p.K >> 5;
-  const int nsl = ksn * nw, sl = ks * nw + wave;
-  const int kt0 = (nkt * sl) / nsl, kt1 = (nkt * (sl + 1)) / nsl;  // <= KTM k-tiles (host-checked)
+  const int nkt = hd.nkt;
+  const int sl = ks * nw + wave;  // of ksn * nw slices
+  const int kt0 = kw_div_by(nkt * sl, hd.slmul), kt1 = kw_div_by(nkt * (sl + 1), hd.slmul);  // <= KTM k-tiles (host-checked)
   const int ktl = max(kt1 - 1, kt0);
-  const int M = p.M;
   const int arow = lane & 15;
   KW_DEC_STAMP_DECL
   KW_DEC_STAMP(0);
@@ -240,20 +257,30 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
   // same weight slice, so it is loaded with the default policy and the second read can hit that XCD's L2; r04's nt
   // loads fetched 1.23x the o / xo weights from memory, profiles/r04p_pmc_fetch.csv)
   bf16x8 w[NCB][KTM], a0[KTM], a1[KTM];
-  load_w_frags<KTM, NCB, H2>(p.W, cg, nkt, kt0, ktl, lane, w);
-  const int wkt0 = (nkt * ks) / ksn, wkt1 = (nkt * (ks + 1)) / ksn;  // this workgroup's k-tiles
-  const int cpr = (wkt1 - wkt0) * 4, cprp = cpr + 1;
-  const bool xlds = p.xlds;
-  // fragment-major x (p.xt row tiles): the fragments are loaded straight into registers with the weights -- no LDS
+  KW_DEC_STAMP_HEAD(1, ktl, hd.W);
+  load_w_frags<KTM, NCB, H2>(hd.W, cg, nkt, kt0, ktl, lane, w);
+  // fragment-major x (xt row tiles): the fragments are loaded straight into registers with the weights -- no LDS
   // image, no barrier
-  if (p.xt) {
-    load_x_frags_tiled<KTM, H2>(p.x, p.xt, kt0, ktl, lane, a0, a1);
-  } else if (xlds) {
+  if (hd.xt) load_x_frags_tiled<KTM, H2>(hd.x, hd.xt, kt0, ktl, lane, a0, a1);
+  // the chunk's descriptor, first needed here: the loads above went out on the launch head alone
+  DecP p = rows_window(p0, p0.zrows * zc, p0.zrows, sizeof(TC));  // (fragment-major: 16-row chunks only)
+  if (ksn > 1) {  // K-split seam: each chunk has its own counters and partial slabs
+    const int ncg = col_groups(p0.N, NCB);  // (the grid's x)
+    p.cnt += zc * ncg;
+    p.slab += (int64_t)zc * ncg * ksn * (NCB * 512);
+  }
+  const int M = p.M;
+  int wkt0 = 0, cpr = 0, cprp = 1;  // the LDS image's first k-tile and row geometry (xlds)
+  const bool xlds = !hd.xt && p.xlds;
+  if (xlds) {
+    wkt0 = (nkt * ks) / ksn;  // this workgroup's k-tiles
+    cpr = ((nkt * (ks + 1)) / ksn - wkt0) * 4;
+    cprp = cpr + 1;
     // <= 16 rows: only the pieces of rows 0..15 (the second row half's fragments then hold stale LDS, and its
     // output rows -- all >= M -- are discarded; every row of an MFMA tile is independent of the others)
     const int ninst = ((M <= 16 ? 16 : 32) * cprp + 63) / 64;
     const float inv = 1.0f / (float)cprp;
-    const bf16_t* xk = p.x + (int64_t)wkt0 * 32;
+    const bf16_t* xk = hd.x + (int64_t)wkt0 * 32;
     for (int j = wave; j < ninst; j += nw) {
       const int pidx = j * 64 + lane;
       int row = (int)(((float)pidx + 0.5f) * inv);
@@ -283,7 +310,7 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
     if (spread ? wave < J : wave == 0) load_resid<NCB, HH>(p, 0, M, cg, lane, hold, EveryJob{});
   }
 
-  if (p.xt) {  // (fragments already in flight)
+  if (hd.xt) {  // (fragments already in flight)
   } else if (xlds) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
@@ -294,7 +321,7 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
       if constexpr (H2) a1[u] = *reinterpret_cast<const bf16x8*>(xs + (pos + 16 * cprp) * 16);
     }
   } else {
-    load_x_frags_rows<KTM, H2>(p.x, p.ldx, M, kt0, ktl, lane, a0, a1);
+    load_x_frags_rows<KTM, H2>(hd.x, p.ldx, M, kt0, ktl, lane, a0, a1);
   }
 
   // 2. MFMA over this wave's k-tiles (raw operand: the LayerNorm is applied in the epilogue)
@@ -472,16 +499,16 @@ __device__ __forceinline__ void dec_linear_body(DecP p, const int ksn, const int
   KW_DEC_STAMP_FLUSH
 }
 
+// The leading scalars are the DecHead of the launch (launch_grid): W, x, xz = the elements x advances per z-chunk, K / 32,
+// xt, the K splits, the waves per workgroup (no blockDim / gridDim read: those are loads from the hidden arguments) and
+// kw_div_mul(ksn * nw); the descriptor comes behind them and is waited for only by what needs it
 template <int KTM, int NCB, bool LNA, int EPI, typename TC, bool H2 = true>
-__global__ __launch_bounds__(512) void dec_linear_kernel(DecP p0, int ksn) {
+__global__ __launch_bounds__(512) void dec_linear_kernel(const bf16x8* W, const bf16_t* x, int64_t xz, int nkt, int xt,
+                                                         int ksn, int nw, uint32_t slmul, DecP p0) {
   // blockIdx.z = 32-row chunk: a launch covers M rows as independent 32-row tiles (their workgroups
   // run concurrently and the repeat weight reads of the later chunks hit the caches)
-  DecP p = rows_window(p0, p0.zrows * blockIdx.z, p0.zrows, sizeof(TC));  // (fragment-major: 16-row chunks only)
-  if (ksn > 1) {  // K-split seam: each chunk has its own counters and partial slabs
-    p.cnt += blockIdx.z * gridDim.x;
-    p.slab += (int64_t)blockIdx.z * gridDim.x * ksn * (NCB * 512);
-  }
-  dec_linear_body<KTM, NCB, LNA, EPI, TC, H2>(p, ksn, blockIdx.x, blockIdx.y, blockDim.x >> 6);
+  const DecHead hd{W, x + xz * blockIdx.z, nkt, xt, slmul};
+  dec_linear_body<KTM, NCB, LNA, EPI, TC, H2>(hd, p0, (int)blockIdx.z, ksn, blockIdx.x, blockIdx.y, nw);
 }
 
 // More than 32 rows without a K split (prefill positions, beam rows): each workgroup keeps its
@@ -1107,7 +1134,12 @@ hipError_t launch_grid(const DecP& q, dim3 grid, dim3 block, size_t shm, int ks,
     if (e != hipSuccess) return e;
     attr = shm;
   }
-  hipLaunchKernelGGL((dec_linear_kernel<KTM, NCB, LNA, EPI, TC, H2>), grid, block, shm, s, q, ks);
+  // the launch head (DecHead): what the first loads need, as leading scalars
+  const int nkt = q.K / 32, nw = (int)block.x / 64, nsl = ks * nw;
+  if (!kw_div_ok((int64_t)nkt * nsl, nsl)) return hipErrorInvalidValue;  // (K within KTM k-tiles a slice is far below)
+  const int64_t xz = q.xt ? (int64_t)q.zrows * 32 : q.zrows * q.ldx;
+  hipLaunchKernelGGL((dec_linear_kernel<KTM, NCB, LNA, EPI, TC, H2>), grid, block, shm, s, q.W, q.x, xz, nkt, q.xt, ks, nw,
+                     kw_div_mul((uint32_t)nsl), q);
   return hipGetLastError();
 }
 

@@ -42,6 +42,15 @@ __device__ __forceinline__ int64_t kw_tiled_off(int m, int n, int T) {
   return ((int64_t)((n >> 5) * T + (m >> 4)) * 64 + (m & 15) + 16 * ((n & 31) >> 3)) * 8 + (n & 7);
 }
 
+// n / d by a multiplier the host forms once (kw_div_mul): a launch passes it beside d, so a kernel's head takes one
+// s_mul_hi_u32 where the division by a launch argument took ~40 scalar instructions.  floor(n / d) is taken as
+// floor((2 n + 1) / (2 d)) -- the same number, and 2 d >= 2 always has a 32-bit multiplier m = floor(2^32 / 2d) + 1
+// (d = 1 included, no branch).  Exact while (2 n + 1) 2 d < 2^32: m 2d = 2^32 + e with 0 < e <= 2d, so
+// floor((2n + 1) m / 2^32) is the quotient as long as (2n + 1) e < 2^32 (kw_div_ok: the host's check)
+__host__ __device__ __forceinline__ uint32_t kw_div_mul(uint32_t d) { return (uint32_t)((1ull << 32) / (2ull * d)) + 1; }
+__host__ __device__ __forceinline__ bool kw_div_ok(int64_t nmax, int64_t d) { return d >= 1 && nmax >= 0 && (2 * nmax + 1) * 2 * d < ((int64_t)1 << 32); }
+__device__ __forceinline__ int kw_div_by(int n, uint32_t mul) { return (int)__umulhi(2u * (uint32_t)n + 1u, mul); }
+
 // the 32-bit LDS address of a __shared__ pointer (inline-asm ds_read operands)
 __device__ __forceinline__ uint32_t lds_u32(const void* p) {
   return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;

@@ -5,25 +5,38 @@
 //   0 entry | 1 its weight + activation loads landed (a vmcnt(0) is inserted there) | 2 MFMA + LayerNorm statistics
 //   done | 3 reduced across waves (and, at the seam, the last arriver's partial sums loaded) | 4 epilogue stores
 //   issued | 5 those stores drained (a vmcnt(0) is inserted)
+// and the launch head of the finishing workgroups: wave 0's first instruction to where its first weight load can be
+// issued ("head").
 // into kw_lab_stamps[workgroup][slot] (a store per stamp: lab timing, within a few percent of the product kernel).
 // Each shape: 32 launches on 32 distinct weight sets captured in one hipGraph, replayed; the stamps of the LAST launch
 // of the last replay are summarised (medians over workgroups, us after the first workgroup's entry).
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -munsafe-fp-atomics tools/lab/chain_stamps.hip \
 //     kotoba-whisper_amd/csrc/capi.hip -o /tmp/chain_stamps && /tmp/chain_stamps
 #include <hip/hip_runtime.h>
-__device__ unsigned long long kw_lab_stamps[2048 * 8];
+// (the workgroup's slot row is indexed from blockIdx alone: gridDim would be one more launch-argument load in the head)
+__device__ unsigned long long kw_lab_stamps[4096 * 8];
+#define KW_LAB_WG ((blockIdx.x * 8 + blockIdx.y) * 2 + blockIdx.z)
 #define KW_DEC_STAMP_DECL
 #define KW_DEC_STAMP(slot)                                                                                         \
   do {                                                                                                             \
     if ((slot) == 1) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                              \
-    if (threadIdx.x == 0)                                                                                          \
-      kw_lab_stamps[(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) * 8 + (slot)] =              \
-          __builtin_amdgcn_s_memrealtime();                                                                        \
+    if (threadIdx.x == 0) kw_lab_stamps[KW_LAB_WG * 8 + (slot)] = __builtin_amdgcn_s_memrealtime();                \
   } while (0)
+// the launch head: 6 the wave's first instruction | 7 its first weight load can be issued (the wave's last k-tile and
+// the weight pointer, which the load's address needs, are in registers: the empty asm takes them as operands); both
+// kept in registers until the flush, so that no store (and no wait for one's operand) stands between them
+#define KW_DEC_STAMP_HEAD(slot, ...) KW_DEC_STAMP_HEAD_##slot(__VA_ARGS__)
+#define KW_DEC_STAMP_HEAD_0() unsigned long long kw_head0_ = __builtin_amdgcn_s_memrealtime(), kw_head1_ = 0
+#define KW_DEC_STAMP_HEAD_1(kt, wp)                \
+  asm volatile("" ::"s"(kt), "s"(wp) : "memory"); \
+  kw_head1_ = __builtin_amdgcn_s_memrealtime()
 #define KW_DEC_STAMP_FLUSH                                                                                         \
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                                 \
-  if (threadIdx.x == 0)                                                                                            \
-    kw_lab_stamps[(blockIdx.x + gridDim.x * (blockIdx.y + gridDim.y * blockIdx.z)) * 8 + 5] = __builtin_amdgcn_s_memrealtime();
+  if (threadIdx.x == 0) {                                                                                          \
+    kw_lab_stamps[KW_LAB_WG * 8 + 5] = __builtin_amdgcn_s_memrealtime();                                           \
+    kw_lab_stamps[KW_LAB_WG * 8 + 6] = kw_head0_;                                                                  \
+    kw_lab_stamps[KW_LAB_WG * 8 + 7] = kw_head1_;                                                                  \
+  }
 #include "../../kotoba-whisper_amd/csrc/declin.hip"
 
 #include <stdio.h>
@@ -41,7 +54,7 @@ static double med(std::vector<double> v) {
 
 struct Shape {
   const char* name;
-  int N, K, resid, ln, gelu, bf16out;
+  int N, K, resid, ln, gelu, bf16out, tiled;  // tiled: x (and a RESID's hb) fragment-major, as the greedy step's plan
 };
 
 // fc2 geometry variants through the production kernels with a chosen Geo (ks K-splits of nw waves x ktm k-tiles)
@@ -77,10 +90,13 @@ int main() {
   hipStream_t s;
   CK(hipStreamCreate(&s));
   const int M = 32, L = 32;
-  const Shape shapes[] = {{"o / xo RESID (row split)", 1280, 1280, 1, 0, 0, 0},
-                          {"fc1 LN + GELU bf16", 5120, 1280, 0, 1, 1, 1},
-                          {"fc2 RESID (split-K seam)", 1280, 5120, 1, 0, 0, 0},
-                          {"qkv LN (two-launch plan)", 3840, 1280, 0, 1, 0, 1}};
+  const Shape shapes[] = {{"o / xo RESID (row split)", 1280, 1280, 1, 0, 0, 0, 0},
+                          {"fc1 LN + GELU bf16", 5120, 1280, 0, 1, 1, 1, 0},
+                          {"fc2 RESID (split-K seam)", 1280, 5120, 1, 0, 0, 0, 0},
+                          {"qkv LN (two-launch plan)", 3840, 1280, 0, 1, 0, 1, 0},
+                          {"o / xo RESID, tiled", 1280, 1280, 1, 0, 0, 0, 1},
+                          {"fc1 LN + GELU bf16, tiled", 5120, 1280, 0, 1, 1, 1, 1},
+                          {"fc2 RESID, tiled", 1280, 5120, 1, 0, 0, 0, 1}};
   bf16_t* x; CK(hipMalloc(&x, 32 * 5120 * 2)); CK(hipMemset(x, 0x3c, 32 * 5120 * 2));
   float* h; CK(hipMalloc(&h, 32 * 5120 * 4)); CK(hipMemset(h, 0, 32 * 5120 * 4));
   bf16_t* hb; CK(hipMalloc(&hb, 32 * 5120 * 2));
@@ -88,7 +104,7 @@ int main() {
   float* bias; CK(hipMalloc(&bias, 5120 * 4)); CK(hipMemset(bias, 0, 5120 * 4));
   float* cs; CK(hipMalloc(&cs, 5120 * 4)); CK(hipMemset(cs, 0, 5120 * 4));
   void* ws; CK(hipMalloc(&ws, 32 << 20)); CK(hipMemset(ws, 0, 32 << 20));
-  std::vector<unsigned long long> st(2048 * 8);
+  std::vector<unsigned long long> st(4096 * 8);
   if (getenv("FC2_GEO")) {  // fc2 K-split geometry sweep, then exit
     std::vector<void*> Ws(L);
     for (int i = 0; i < L; ++i) { CK(hipMalloc(&Ws[i], (size_t)1280 * 5120 * 2)); CK(hipMemset(Ws[i], 0x3c, (size_t)1280 * 5120 * 2)); }
@@ -109,8 +125,8 @@ int main() {
       CK(hipMemset(Ws[i], 0x3c, (size_t)sh.N * sh.K * 2));
     }
     kw_dec_linear_args a{};
-    a.x = x; a.ldx = sh.K; a.ln = sh.ln; a.ln_eps = 1e-5f; a.ln_colsum = cs; a.bias = bias;
-    a.epilogue = sh.resid ? KW_EPI_RESID : KW_EPI_STORE;
+    a.x = x; a.ldx = sh.tiled ? KW_LD_TILED : sh.K; a.ln = sh.ln; a.ln_eps = 1e-5f; a.ln_colsum = cs; a.bias = bias;
+    a.epilogue = sh.resid ? (sh.tiled ? KW_EPI_RESID | KW_EPI_HB_TILED : KW_EPI_RESID) : KW_EPI_STORE;
     a.C = sh.resid ? nullptr : C; a.ldc = sh.N; a.c_dtype = sh.bf16out ? KW_DT_BF16 : KW_DT_F32;
     a.gelu = sh.gelu; a.scale = 1.f; a.scale_cols = 0;
     a.h = sh.resid ? h : nullptr; a.hb = sh.resid ? hb : nullptr; a.ldh = sh.N;
@@ -131,28 +147,30 @@ int main() {
     float ms; CK(hipEventElapsedTime(&ms, e0, e1));
     for (int rep = 0; rep < 3; ++rep) {
       CK(hipMemsetAsync(ws, 0, 4096 * 4, s));  // (arrival counters are re-armed by the kernels anyway)
-      unsigned long long zero[2048 * 8] = {};
+      static unsigned long long zero[4096 * 8] = {};
       CK(hipMemcpyToSymbolAsync(HIP_SYMBOL(kw_lab_stamps), zero, sizeof(zero), 0, hipMemcpyHostToDevice, s));
       CK(hipGraphLaunch(ge, s));
       CK(hipStreamSynchronize(s));
       CK(hipMemcpyFromSymbol(st.data(), HIP_SYMBOL(kw_lab_stamps), sizeof(unsigned long long) * st.size()));
       unsigned long long t0 = ~0ull, tend = 0;
       int n = 0;
-      for (int w = 0; w < 2048; ++w)
+      for (int w = 0; w < 4096; ++w)
         if (st[w * 8]) { t0 = std::min(t0, st[w * 8]); ++n; }
-      std::vector<double> ph[6];
+      std::vector<double> ph[6], head;
       int done = 0;
-      for (int w = 0; w < 2048; ++w) {
+      for (int w = 0; w < 4096; ++w) {
         const unsigned long long* q = &st[w * 8];
         if (!q[0]) continue;
+        if (q[6] && q[7]) head.push_back((double)(q[7] - q[6]) / 100.0);
         for (int k = 0; k < 6; ++k)
           if (q[k]) ph[k].push_back((double)(q[k] - t0) / 100.0);
         if (q[5]) { tend = std::max(tend, q[5]); ++done; }
       }
       printf("%-28s %6.2f us/launch | WGs %4d (finishing %4d) | median us after first entry: entry %.2f loads %.2f mfma %.2f "
-             "reduced %.2f stores-issued %.2f drained %.2f | last drained %.2f | entry spread %.2f\n",
+             "reduced %.2f stores-issued %.2f drained %.2f | last drained %.2f | entry spread %.2f | head median %.2f max %.2f\n",
              sh.name, ms * 1000.f / (20 * L), n, done, med(ph[0]), med(ph[1]), med(ph[2]), med(ph[3]), med(ph[4]),
-             med(ph[5]), (tend - t0) / 100.0, ph[0].empty() ? 0.0 : (*std::max_element(ph[0].begin(), ph[0].end())));
+             med(ph[5]), (tend - t0) / 100.0, ph[0].empty() ? 0.0 : (*std::max_element(ph[0].begin(), ph[0].end())), med(head),
+             head.empty() ? 0.0 : *std::max_element(head.begin(), head.end()));
     }
     CK(hipGraphExecDestroy(ge)); CK(hipGraphDestroy(g));
     for (void* p : Ws) CK(hipFree(p));

@@ -33,7 +33,7 @@ float run(const char* name, DecP p, int nw, int ks, std::vector<const bf16x8*>& 
   const size_t shm = x_lds_bytes_for(p.K / 32, ks, p.xlds);
   CK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dec_linear_kernel<KTM, NCB, LNA, EPI, TC>),
                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)shm));
-  for (auto* W : Ws) { p.W = W; hipLaunchKernelGGL((dec_linear_kernel<KTM, NCB, LNA, EPI, TC>), grid, block, shm, s, p, ks); }
+  for (auto* W : Ws) { p.W = W; CK((launch_grid<KTM, NCB, LNA, EPI, TC, true>(p, grid, block, shm, ks, s))); }  // (forms the launch head)
   CK(hipStreamEndCapture(s, &g));
   CK(hipGraphInstantiate(&ge, g, nullptr, nullptr, 0));
   for (int i = 0; i < 3; ++i) CK(hipGraphLaunch(ge, s));

@@ -6,6 +6,7 @@
 //                          (before the merge barrier) | 7 output stored
 // into kw_lab_stamps[workgroup][slot].  32 launches on 32 layers' weights and caches captured in one hipGraph,
 // replayed; the stamps of the LAST launch are summarised (medians over workgroups, us after the first entry).
+// Four passes: L = 68 and 132 from a row-major x / out, then from fragment-major ones (the greedy step's plan).
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 -munsafe-fp-atomics tools/lab/qkv_stamps.hip \
 //     kotoba-whisper_amd/csrc/capi.hip -o /tmp/qkv_stamps && /tmp/qkv_stamps
 #include <hip/hip_runtime.h>
@@ -51,10 +52,11 @@ int main() {
     CK(hipMalloc(&vc[i], cache)); CK(hipMemset(vc[i], 0x3c, cache));
   }
   std::vector<unsigned long long> st(1024 * 8);
-  for (int L : {68, 132}) {
+  for (int pass = 0; pass < 4; ++pass) {  // row-major x / out, then fragment-major (the greedy step's plan)
+    const int L = pass & 1 ? 132 : 68, tiled = pass >> 1;
     CK(hipMemcpy(cur, &L, 4, hipMemcpyHostToDevice));
     kw_dec_qkv_self_args a{};
-    a.x = x; a.ldx = d; a.ln_eps = 1e-5f; a.ln_colsum = cs; a.bias = bias; a.scale = 0.125f;
+    a.x = x; a.ldx = tiled ? KW_LD_TILED : d; a.ln_eps = 1e-5f; a.ln_colsum = cs; a.bias = bias; a.scale = 0.125f;
     a.M = M; a.d = d; a.H = H; a.t_max = T; a.cur_len = cur; a.out = out; a.workspace = ws; a.ws_bytes = wsb;
     hipGraph_t g; hipGraphExec_t ge;
     CK(hipStreamBeginCapture(s, hipStreamCaptureModeGlobal));
@@ -86,9 +88,10 @@ int main() {
       for (int w = 0; w < 1024; ++w)
         for (int k = 0; k < 8; ++k)
           if (st[w * 8 + k]) ph[k].push_back((double)(st[w * 8 + k] - t0) / 100.0);
-      printf("L %3d: %6.2f us/launch | proj WGs %zu: entry %.2f (last %.2f) mfma %.2f reduced+published %.2f (last %.2f) | "
+      printf("%s L %3d: %6.2f us/launch | proj WGs %zu: entry %.2f (last %.2f) mfma %.2f reduced+published %.2f (last %.2f) | "
              "pair WGs %zu: entry %.2f (last %.2f) granules %.2f (last %.2f) attention %.2f out %.2f (last %.2f) | n_lin %d\n",
-             L, ms * 1000.f / (20 * NL), ph[0].size(), med(ph[0]), mx(ph[0]), med(ph[1]), med(ph[2]), mx(ph[2]), ph[4].size(),
+             tiled ? "tiled" : "rows ", L, ms * 1000.f / (20 * NL), ph[0].size(), med(ph[0]), mx(ph[0]), med(ph[1]), med(ph[2]),
+             mx(ph[2]), ph[4].size(),
              med(ph[4]), mx(ph[4]), med(ph[5]), mx(ph[5]), med(ph[6]), med(ph[7]), mx(ph[7]), n_lin);
     }
     CK(hipGraphExecDestroy(ge)); CK(hipGraphDestroy(g));
