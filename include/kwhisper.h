@@ -702,6 +702,51 @@ int kw_repeat_process(float* scores, int64_t R, int64_t V, const int64_t* ids, i
  * floats of the row's workspace record, and the split launch reads them -- kernel order, no in-launch hand-off. */
 int kw_beam_logprobs_rep(const kw_beam_logprobs_args* args, float penalty, int32_t ngram, kw_stream_t stream);
 
+/* ---- sequence_bias / bad_words_ids (additive, ABI 112 unchanged) ------------------------------------------
+ * GenerationMixin's SequenceBiasLogitsProcessor and NoBadWordsLogitsProcessor (TF generation/logits_process.py:
+ * 1288-1319, 1450-1467): the first runs immediately BEFORE the repetition pair, the second immediately AFTER it and
+ * before the Whisper processors (TF generation/utils.py:1154-1155, 1174-1183, 1207-1213).  A processor is a set of
+ * (token sequence, f32 value) entries; NoBadWords is SequenceBias with every value -inf.  For a row with history
+ * ids[r][0 .. L), L = *cur_len (a DEVICE scalar, so a captured step replays; the forced tokens, a conditioned pass's
+ * previous text and its left pads are all part of the history):
+ *   an entry of n tokens is considered when n <= L; n == 1 always applies; n > 1 applies when the history's last n-1
+ *   tokens equal the entry's first n-1.  The bias of a token starts at 0, takes its length-1 entry's value, and every
+ *   applying longer entry that ends in the token adds its value, in the processor's own order, in f32; then
+ *   score[token] = score[token] + bias.  Infinite values are ordinary floats: -inf bans, +inf + -inf is NaN.
+ * The table is the processor flattened on the host (kwhisper/seq_bias.py builds it), all arrays in DEVICE memory:
+ *   entries grouped by their last token with a stable sort, groups in strictly ascending token order; inside a group the
+ *   length-1 entry first, the others in the processor's order -- so one reader walking a group forms the reference's
+ *   sum.  Every token id of the table is in [0, V): the host checks it, the kernels never dereference one that is not.
+ * Caps: n_seq <= KW_SEQ_BIAS_MAX_SEQS entries of at most KW_SEQ_BIAS_MAX_LEN tokens each (max_len states the table's
+ * longest); beyond them KW_EUNSUPPORTED, nothing is launched. */
+#define KW_SEQ_BIAS_MAX_SEQS 4096
+#define KW_SEQ_BIAS_MAX_LEN 32
+typedef struct {
+  const int32_t* tokens;     /* [seq_off[n_seq]] the entries' tokens, back to back */
+  const int32_t* seq_off;    /* [n_seq + 1] entry s is tokens[seq_off[s] .. seq_off[s + 1]) */
+  const float* values;       /* [n_seq] */
+  const int32_t* group_off;  /* [n_groups + 1] group g is entries group_off[g] .. group_off[g + 1) */
+  const int32_t* group_tok;  /* [n_groups] the groups' last tokens, strictly ascending */
+  int32_t n_seq, n_groups;
+  int32_t max_len;           /* the longest entry's token count */
+} kw_seq_bias_table;
+
+/* In place on f32 scores [R][V], one workgroup per row, a thread per group: it tests the group's entries against the
+ * tail of the row's history, sums the applying values in order and adds the sum to its token -- one writer per element,
+ * no float atomics; an element of no group is not touched.  The greedy and sampled tails run it on the raw logits:
+ * with a sequence_bias table before kw_repeat_process, with a bad_words_ids table after it.  ids / ids_stride /
+ * cur_len as kw_repeat_process reads them (L = min(*cur_len, ids_stride)).  n_seq == 0 launches nothing. */
+int kw_seq_bias_process(float* scores, int64_t R, int64_t V, const int64_t* ids, int64_t ids_stride,
+                        const int32_t* cur_len, const kw_seq_bias_table* table, kw_stream_t stream);
+
+/* kw_beam_logprobs_rep with the two processors around the repetition pair, on every element's log-prob: the
+ * sequence_bias table's sum is added before the penalty, the bad_words_ids table's applying entries are OR-ed into the
+ * n-gram ban bitset (a ban is -inf whatever came before).  Either table may be NULL or empty; with both empty the
+ * launch IS kw_beam_logprobs_rep's.  Each workgroup builds its row's matches once in LDS (a vocabulary bitset and one
+ * sum per group).  V <= 65536 (KW_EUNSUPPORTED beyond), workspace and launches as kw_beam_logprobs_rep. */
+int kw_beam_logprobs_proc(const kw_beam_logprobs_args* args, float penalty, int32_t ngram,
+                          const kw_seq_bias_table* bias, const kw_seq_bias_table* bad_words, kw_stream_t stream);
+
 /* ---- distillation loss on the teacher's logits (additive, ABI 112 unchanged) --------------------------
  * The temperature KL of kotoba-whisper's train_step (run_distillation.py:614-622, 652-657): with
  * p = softmax(teacher / T) and q = softmax(student / T) over the V columns of a row,

@@ -18,8 +18,10 @@
 // All arithmetic is fp32 in the reference's order (log-prob + score, -1e9 masks, score /
 // len**length_penalty); every top-k breaks ties by the lower flat index.
 #include <math.h>
+#include <stdio.h>
 
 #include "processors.h"
+#include "seqbias.h"
 
 namespace {
 
@@ -154,9 +156,59 @@ __device__ __forceinline__ float rep_apply(const uint32_t* hist, const uint32_t*
   return y;
 }
 
-template <bool REP>
-__device__ __forceinline__ void beam_logprobs_body(const kw_beam_logprobs_args& a, float penalty, int ngram) {
+// ---- sequence_bias / bad_words_ids on the log-probs (kw_beam_logprobs_proc; the MODE 2 instantiations).
+// SequenceBiasLogitsProcessor runs just ahead of the repetition pair, NoBadWordsLogitsProcessor just behind it
+// (TF/generation/utils.py:1154-1155, 1207-1213).  Each workgroup walks both tables once against its row's history
+// (seqbias.h): a sequence_bias group with an applying entry leaves its f32 sum in sb_sum[group] and its token's bit in
+// sb_bits; a bad_words_ids group with an applying entry sets its token's bit in the n-gram ban bitset (-inf whatever
+// came before).  Groups are in ascending token order, so an element whose bit is set finds its group by bisection --
+// a handful of elements per row.
+template <int NT>
+__device__ __forceinline__ void seq_tables(uint32_t* sb_bits, float* sb_sum, uint32_t* ban, const kw_seq_bias_table& sb,
+                                           const kw_seq_bias_table& bw, const int64_t* __restrict__ ids, int L, int V) {
+  const int tid = threadIdx.x;
+  const int nw = (V + 31) >> 5;
+  for (int i = tid; i < nw; i += NT) sb_bits[i] = 0;
+  __syncthreads();
+  for (int g = tid; g < sb.n_groups; g += NT) {
+    const int v = sb.group_tok[g];
+    if (v < 0 || v >= V) continue;
+    bool hit;
+    const float b = kwsb::group_bias(sb, g, ids, L, &hit);
+    if (!hit) continue;
+    sb_sum[g] = b;
+    atomicOr(&sb_bits[v >> 5], 1u << (v & 31));
+  }
+  for (int g = tid; g < bw.n_groups; g += NT) {
+    const int v = bw.group_tok[g];
+    if (v < 0 || v >= V) continue;
+    bool hit;
+    kwsb::group_bias(bw, g, ids, L, &hit);
+    if (hit) atomicOr(&ban[v >> 5], 1u << (v & 31));
+  }
+  __syncthreads();
+}
+// (y + bias, f32, ahead of rep_apply)
+__device__ __forceinline__ float seq_bias_apply(const uint32_t* sb_bits, const float* sb_sum, const kw_seq_bias_table& sb,
+                                                int v, float y) {
+  if (!((sb_bits[v >> 5] >> (v & 31)) & 1u)) return y;
+  int lo = 0, hi = sb.n_groups - 1;  // the bit says v is one of group_tok[0 .. n_groups)
+  while (lo < hi) {
+    const int mid = (lo + hi) >> 1;
+    if (sb.group_tok[mid] < v) lo = mid + 1;
+    else hi = mid;
+  }
+  return y + sb_sum[lo];
+}
+
+// MODE 0: the plain kernels; 1: REP (kw_beam_logprobs_rep); 2: REP between the two sequence tables (.._proc)
+template <int MODE>
+__device__ __forceinline__ void beam_logprobs_body(const kw_beam_logprobs_args& a, float penalty, int ngram,
+                                                   const kw_seq_bias_table* sb, const kw_seq_bias_table* bw) {
+  constexpr bool REP = MODE >= 1, PROC = MODE == 2;
   __shared__ uint32_t rep_hist[REP ? REP_WORDS : 1], rep_ban[REP ? REP_WORDS : 1];
+  __shared__ uint32_t sb_bits[PROC ? REP_WORDS : 1];
+  __shared__ float sb_sum[PROC ? KW_SEQ_BIAS_MAX_SEQS : 1];
   __shared__ float shf[ST / 64];
   __shared__ int shi[ST / 64];
   __shared__ RowState st_sh;
@@ -180,8 +232,10 @@ __device__ __forceinline__ void beam_logprobs_body(const kw_beam_logprobs_args& 
   s = wg_sum<ST>(s, shf);
   const float ls = logf(s);
   if constexpr (REP) rep_bitsets<ST>(rep_hist, rep_ban, ids, L, V, penalty, ngram);
+  if constexpr (PROC) seq_tables<ST>(sb_bits, sb_sum, rep_ban, *sb, *bw, ids, L, V);
   auto lp = [&](int v) {
-    const float y = (x[v] - m) - ls;
+    float y = (x[v] - m) - ls;
+    if constexpr (PROC) y = seq_bias_apply(sb_bits, sb_sum, *sb, v, y);
     if constexpr (REP) return rep_apply(rep_hist, rep_ban, penalty, v, y);
     return y;
   };
@@ -241,10 +295,14 @@ __device__ __forceinline__ void beam_logprobs_body(const kw_beam_logprobs_args& 
 
 // (the kernels keep one symbol each: REP is a flag of the shared body, the plain launch's code is as it was)
 __global__ __launch_bounds__(ST) void beam_logprobs_kernel(kw_beam_logprobs_args a) {
-  beam_logprobs_body<false>(a, 1.0f, 0);
+  beam_logprobs_body<0>(a, 1.0f, 0, nullptr, nullptr);
 }
 __global__ __launch_bounds__(ST) void beam_lp_rep_kernel(kw_beam_logprobs_args a, float penalty, int ngram) {
-  beam_logprobs_body<true>(a, penalty, ngram);
+  beam_logprobs_body<1>(a, penalty, ngram, nullptr, nullptr);
+}
+__global__ __launch_bounds__(ST) void beam_lp_proc_kernel(kw_beam_logprobs_args a, float penalty, int ngram,
+                                                          kw_seq_bias_table sb, kw_seq_bias_table bw) {
+  beam_logprobs_body<2>(a, penalty, ngram, &sb, &bw);
 }
 
 // ---- split-row variant: a row over NSPLIT workgroups (the one-workgroup kernel above walks a whole
@@ -285,9 +343,13 @@ __device__ __forceinline__ void bl_argmax(float& best, int& bi, int& bt, float* 
 // turns its logits into penalised / banned log-probs up front, and the merge takes the candidates' values as they
 // are instead of normalising them.  (Each slice taking the normaliser itself, eight reads of every row, cost 77 us at
 // R = 160, V = 51866 -- more than the whole plain launch.)
-template <bool REP>
-__device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_args& a, float penalty, int ngram) {
+template <int MODE>
+__device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_args& a, float penalty, int ngram,
+                                                         const kw_seq_bias_table* sb, const kw_seq_bias_table* bw) {
+  constexpr bool REP = MODE >= 1, PROC = MODE == 2;
   __shared__ uint32_t rep_hist[REP ? REP_WORDS : 1], rep_ban[REP ? REP_WORDS : 1];
+  __shared__ uint32_t sb_bits[PROC ? REP_WORDS : 1];
+  __shared__ float sb_sum[PROC ? KW_SEQ_BIAS_MAX_SEQS : 1];
   __shared__ RowState st_sh;
   __shared__ float pub[BPART];
   if (*a.done) return;
@@ -315,10 +377,15 @@ __device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_
     const float* nrm = reinterpret_cast<const float*>(a.workspace) + (int64_t)r * NSPLIT * BPART + REP_NORM;
     const float m = nrm[0], ls = nrm[1];  // (beam_rep_norm_kernel, the launch before this one)
     rep_bitsets<SPLIT_T>(rep_hist, rep_ban, ids, L, V, penalty, ngram);
+    if constexpr (PROC) seq_tables<SPLIT_T>(sb_bits, sb_sum, rep_ban, *sb, *bw, ids, L, V);
 #pragma unroll
     for (int u = 0; u < SUNR; ++u) {
       const int v = v0 + tid + u * SPLIT_T;
-      if (v < v1) xv[u] = rep_apply(rep_hist, rep_ban, penalty, v, (xv[u] - m) - ls);
+      if (v < v1) {
+        float y = (xv[u] - m) - ls;
+        if constexpr (PROC) y = seq_bias_apply(sb_bits, sb_sum, *sb, v, y);
+        xv[u] = rep_apply(rep_hist, rep_ban, penalty, v, y);
+      }
     }
   }
   // row state from the history (kwp::history_row_state's, with no dependent load): the last timestamp position
@@ -585,10 +652,14 @@ __device__ __forceinline__ void beam_logprobs_split_body(const kw_beam_logprobs_
 }
 
 __global__ __launch_bounds__(SPLIT_T) void beam_logprobs_split_kernel(kw_beam_logprobs_args a) {
-  beam_logprobs_split_body<false>(a, 1.0f, 0);
+  beam_logprobs_split_body<0>(a, 1.0f, 0, nullptr, nullptr);
 }
 __global__ __launch_bounds__(SPLIT_T) void beam_lp_rep_split_kernel(kw_beam_logprobs_args a, float penalty, int ngram) {
-  beam_logprobs_split_body<true>(a, penalty, ngram);
+  beam_logprobs_split_body<1>(a, penalty, ngram, nullptr, nullptr);
+}
+__global__ __launch_bounds__(SPLIT_T) void beam_lp_proc_split_kernel(kw_beam_logprobs_args a, float penalty, int ngram,
+                                                                     kw_seq_bias_table sb, kw_seq_bias_table bw) {
+  beam_logprobs_split_body<2>(a, penalty, ngram, &sb, &bw);
 }
 // the row's log_softmax normaliser, as beam_logprobs_body takes it, for the launch above
 __global__ __launch_bounds__(ST) void beam_rep_norm_kernel(kw_beam_logprobs_args a) {
@@ -907,6 +978,40 @@ extern "C" int kw_beam_logprobs_rep(const kw_beam_logprobs_args* a, float penalt
   } else {
     hipLaunchKernelGGL(beam_lp_rep_kernel, dim3((unsigned)a->R), dim3(ST), 0, (hipStream_t)stream, *a, penalty,
                        (int)ngram);
+  }
+  KW_CHECK_LAUNCH();
+  return KW_OK;
+}
+
+extern "C" int kw_beam_logprobs_proc(const kw_beam_logprobs_args* a, float penalty, int32_t ngram,
+                                     const kw_seq_bias_table* bias, const kw_seq_bias_table* bad_words,
+                                     kw_stream_t stream) {
+  const char* why = "";
+  int rc = kwsb::table_check(bias, &why);
+  if (!rc) rc = kwsb::table_check(bad_words, &why);
+  if (rc) {
+    char msg[160];
+    snprintf(msg, sizeof(msg), "kw_beam_logprobs_proc: %s", why);
+    return kw_set_error_msg(rc, msg);
+  }
+  if (kwsb::table_empty(bias) && kwsb::table_empty(bad_words))
+    return kw_beam_logprobs_rep(a, penalty, ngram, stream);  // no table: that very launch
+  if (!a || !a->logits || !a->suppress_mask || !a->ids || !a->cur_len || !a->cand_val || !a->cand_idx || !a->done ||
+      a->R <= 0 || a->V <= 0 || a->k < 1 || a->k > KMAX || (a->n_begin_suppress > 0 && !a->begin_suppress) ||
+      !(penalty > 0.f) || !isfinite(penalty) || ngram < 0)
+    return kw_set_error_msg(KW_EINVAL,
+                            "kw_beam_logprobs_proc: invalid arguments (k <= 16, penalty > 0 and finite, ngram >= 0)");
+  if (a->V > REP_VMAX) return kw_set_error_msg(KW_EUNSUPPORTED, "kw_beam_logprobs_proc: V > 65536");
+  const kw_seq_bias_table none{};  // (n_groups 0: its arrays are never read)
+  const kw_seq_bias_table sb = kwsb::table_empty(bias) ? none : *bias;
+  const kw_seq_bias_table bw = kwsb::table_empty(bad_words) ? none : *bad_words;
+  if (a->workspace && a->ws_bytes >= kw_beam_logprobs_workspace(a->R) && a->V <= (int64_t)NSPLIT * SPLIT_T * SUNR) {
+    hipLaunchKernelGGL(beam_rep_norm_kernel, dim3((unsigned)a->R), dim3(ST), 0, (hipStream_t)stream, *a);
+    hipLaunchKernelGGL(beam_lp_proc_split_kernel, dim3((unsigned)a->R, NSPLIT), dim3(SPLIT_T), 0, (hipStream_t)stream,
+                       *a, penalty, (int)ngram, sb, bw);
+  } else {
+    hipLaunchKernelGGL(beam_lp_proc_kernel, dim3((unsigned)a->R), dim3(ST), 0, (hipStream_t)stream, *a, penalty,
+                       (int)ngram, sb, bw);
   }
   KW_CHECK_LAUNCH();
   return KW_OK;

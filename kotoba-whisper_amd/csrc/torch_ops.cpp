@@ -548,11 +548,39 @@ void dec_lm_greedy(const Tensor& x, const Tensor& W, const optional<Tensor>& bia
 
 // ---- beam search step ---------------------------------------------------------------------------------
 // cfg = [return_timestamps, ts_begin, no_ts_id, eos_id, max_initial_ts, begin_index, k]
-// (penalty / ngram: kw_beam_logprobs_rep when rep, else kw_beam_logprobs)
+// A kw_seq_bias_table from its five device arrays [tokens, seq_off, values, group_off, group_tok] (an empty list: no
+// table, n_seq 0) and the longest entry's token count.
+kw_seq_bias_table seq_table(const std::vector<Tensor>& t, int64_t max_len, const char* w) {
+  kw_seq_bias_table o{};
+  if (t.empty()) return o;
+  TORCH_CHECK_VALUE(t.size() == 5, w, ": a sequence table is [tokens, seq_off, values, group_off, group_tok]");
+  for (const Tensor& x : t) {
+    dev(x, w);
+    TORCH_CHECK_VALUE(x.dim() == 1 && x.is_contiguous(), w, ": sequence table arrays must be contiguous vectors");
+  }
+  TORCH_CHECK_VALUE(t[0].scalar_type() == at::kInt && t[1].scalar_type() == at::kInt &&
+                        t[2].scalar_type() == at::kFloat && t[3].scalar_type() == at::kInt &&
+                        t[4].scalar_type() == at::kInt,
+                    w, ": sequence table arrays are int32 but the float32 values");
+  const int64_t n_seq = t[2].numel(), n_groups = t[4].numel();
+  TORCH_CHECK_VALUE(n_seq >= 1 && n_seq <= INT32_MAX && t[1].numel() == n_seq + 1 && t[3].numel() == n_groups + 1 &&
+                        t[0].numel() >= n_seq && max_len >= 1 && max_len <= INT32_MAX,
+                    w, ": sequence table arrays disagree in length");
+  o.tokens = ptr<const int32_t>(t[0]);
+  o.seq_off = ptr<const int32_t>(t[1]);
+  o.values = ptr<const float>(t[2]);
+  o.group_off = ptr<const int32_t>(t[3]);
+  o.group_tok = ptr<const int32_t>(t[4]);
+  o.n_seq = (int32_t)n_seq, o.n_groups = (int32_t)n_groups, o.max_len = (int32_t)max_len;
+  return o;
+}
+
+// (penalty / ngram: kw_beam_logprobs_rep when rep, else kw_beam_logprobs; sb / bw: kw_beam_logprobs_proc)
 void beam_logprobs_impl(const char* w, bool rep, const Tensor& logits, const Tensor& suppress_mask,
                         const optional<Tensor>& begin_suppress, const Tensor& ids, const Tensor& cur_len, Tensor& cand_val,
                         Tensor& cand_idx, const Tensor& done, optional<Tensor> workspace, std::vector<int64_t> cfg,
-                        double penalty, int64_t ngram) {
+                        double penalty, int64_t ngram, const kw_seq_bias_table* sb = nullptr,
+                        const kw_seq_bias_table* bw = nullptr) {
   dev(logits, w), dev(suppress_mask, w), dev(begin_suppress, w), dev(ids, w), dev(cur_len, w);
   dev(cand_val, w), dev(cand_idx, w), dev(done, w), dev(workspace, w);
   TORCH_CHECK_VALUE(cfg.size() == 7, w, ": cfg must hold 7 integers");
@@ -576,7 +604,10 @@ void beam_logprobs_impl(const char* w, bool rep, const Tensor& logits, const Ten
   a.workspace = optr<void>(workspace);
   a.ws_bytes = workspace.has_value() ? (size_t)workspace->numel() * workspace->element_size() : 0;
   c10::DeviceGuard g(logits.device());
-  if (rep) {
+  if (sb) {
+    TORCH_CHECK_VALUE(ngram >= INT32_MIN && ngram <= INT32_MAX, w, ": ngram out of range");
+    check(kw_beam_logprobs_proc(&a, (float)penalty, (int32_t)ngram, sb, bw, stream_of(logits)), w);
+  } else if (rep) {
     TORCH_CHECK_VALUE(ngram >= INT32_MIN && ngram <= INT32_MAX, w, ": ngram out of range");
     check(kw_beam_logprobs_rep(&a, (float)penalty, (int32_t)ngram, stream_of(logits)), w);
   } else {
@@ -597,6 +628,35 @@ void beam_logprobs_rep(const Tensor& logits, const Tensor& suppress_mask, const 
                        optional<Tensor> workspace, std::vector<int64_t> cfg, double penalty, int64_t ngram) {
   beam_logprobs_impl("kw_beam_logprobs_rep", true, logits, suppress_mask, begin_suppress, ids, cur_len, cand_val,
                      cand_idx, done, workspace, cfg, penalty, ngram);
+}
+
+// kw_beam_logprobs_rep between sequence_bias and bad_words_ids (tables as seq_table takes them)
+void beam_logprobs_proc(const Tensor& logits, const Tensor& suppress_mask, const optional<Tensor>& begin_suppress,
+                        const Tensor& ids, const Tensor& cur_len, Tensor& cand_val, Tensor& cand_idx, const Tensor& done,
+                        optional<Tensor> workspace, std::vector<int64_t> cfg, double penalty, int64_t ngram,
+                        std::vector<Tensor> bias, int64_t bias_max_len, std::vector<Tensor> bad_words,
+                        int64_t bad_max_len) {
+  const char* w = "kw_beam_logprobs_proc";
+  const kw_seq_bias_table sb = seq_table(bias, bias_max_len, w), bw = seq_table(bad_words, bad_max_len, w);
+  beam_logprobs_impl(w, true, logits, suppress_mask, begin_suppress, ids, cur_len, cand_val, cand_idx, done, workspace,
+                     cfg, penalty, ngram, &sb, &bw);
+}
+
+// ---- sequence_bias / bad_words_ids in place on f32 scores [R][V] -------------------------------------------
+void seq_bias_process(Tensor& scores, const Tensor& ids, const Tensor& cur_len, std::vector<Tensor> table,
+                      int64_t max_len) {
+  const char* w = "kw_seq_bias_process";
+  dev(scores, w), dev(ids, w), dev(cur_len, w);
+  TORCH_CHECK_VALUE(scores.dim() == 2 && scores.is_contiguous() && scores.scalar_type() == at::kFloat,
+                    "kw_seq_bias_process: scores must be a contiguous (R, V) float32 tensor");
+  TORCH_CHECK_VALUE(ids.dim() == 2 && ids.scalar_type() == at::kLong && ids.stride(1) == 1 &&
+                        ids.size(0) >= scores.size(0) && cur_len.scalar_type() == at::kInt && cur_len.numel() >= 1,
+                    "kw_seq_bias_process: ids int64 [R][ids_stride], cur_len int32 [1]");
+  const kw_seq_bias_table t = seq_table(table, max_len, w);
+  c10::DeviceGuard g(scores.device());
+  check(kw_seq_bias_process(ptr<float>(scores), scores.size(0), scores.size(1), ptr<const int64_t>(ids), ids.stride(0),
+                            ptr<const int32_t>(cur_len), &t, stream_of(scores)),
+        w);
 }
 
 // ---- repetition_penalty / no_repeat_ngram_size in place on f32 scores [R][V] ------------------------------
@@ -883,6 +943,10 @@ TORCH_LIBRARY(kw, m) {
         "Tensor(a!) cand_val, Tensor(b!) cand_idx, Tensor done, Tensor(c!)? workspace, int[] cfg, float penalty, "
         "int ngram) -> ()");
   m.def("repeat_process(Tensor(a!) scores, Tensor ids, Tensor cur_len, float penalty, int ngram) -> ()");
+  m.def("beam_logprobs_proc(Tensor logits, Tensor suppress_mask, Tensor? begin_suppress, Tensor ids, Tensor cur_len, "
+        "Tensor(a!) cand_val, Tensor(b!) cand_idx, Tensor done, Tensor(c!)? workspace, int[] cfg, float penalty, "
+        "int ngram, Tensor[] bias, int bias_max_len, Tensor[] bad_words, int bad_max_len) -> ()");
+  m.def("seq_bias_process(Tensor(a!) scores, Tensor ids, Tensor cur_len, Tensor[] table, int max_len) -> ()");
   m.def("beam_select(Tensor cand_val, Tensor cand_idx, Tensor(a!) ids, Tensor(b!)? bp, Tensor(c!) run_scores, "
         "Tensor(d!) fin_seq, Tensor(e!) fin_score, Tensor(f!) fin_len, Tensor(g!) fin_flag, Tensor(h!) unsat, "
         "Tensor(i!) cur_len, Tensor(j!) counter, Tensor(k!) go, Tensor(l!) done, Tensor(m!) item_flags, int[] cfg, "
@@ -926,6 +990,8 @@ TORCH_LIBRARY_IMPL(kw, CUDA, m) {
   m.impl("beam_logprobs", &beam_logprobs);
   m.impl("beam_logprobs_rep", &beam_logprobs_rep);
   m.impl("repeat_process", &repeat_process);
+  m.impl("beam_logprobs_proc", &beam_logprobs_proc);
+  m.impl("seq_bias_process", &seq_bias_process);
   m.impl("beam_select", &beam_select);
   m.impl("beam_select_parents", &beam_select_parents);
   m.impl("align_weights_rows", &align_weights_rows);

@@ -23,6 +23,7 @@ TORCH_OPS = ("log_mel", "mel_to_time_major", "gemm", "dec_linear", "pack_weight"
              "self_attn_step", "dec_qkv_self", "dec_xq_cross", "cross_attn_step", "greedy_step", "sample_step", "dec_lm_greedy",
              "beam_logprobs", "beam_select", "align_capture", "align_weights", "align_reduce", "dtw", "cross_kv_quant",
              "cross_attn_step_fp8", "dec_xq_cross_fp8", "self_attn_step_masked", "repeat_process", "beam_logprobs_rep",
+             "seq_bias_process", "beam_logprobs_proc",
              "beam_select_parents", "align_weights_rows", "spec_accept", "kd_loss")
 
 KW_OK, KW_EINVAL, KW_EHIP, KW_EUNSUPPORTED = 0, 1, 2, 3
@@ -139,6 +140,14 @@ class KdLossArgs(ctypes.Structure):
     ]
 
 
+class SeqBiasTable(ctypes.Structure):
+    """kw_seq_bias_table: a sequence_bias / bad_words_ids processor flattened (kwhisper/seq_bias.py)."""
+    _fields_ = [
+        ("tokens", c_vp), ("seq_off", c_vp), ("values", c_vp), ("group_off", c_vp), ("group_tok", c_vp),
+        ("n_seq", c_i32), ("n_groups", c_i32), ("max_len", c_i32),
+    ]
+
+
 class BeamLogprobsArgs(ctypes.Structure):
     _fields_ = [
         ("logits", c_vp), ("R", c_i64), ("V", c_i64),
@@ -222,6 +231,9 @@ EXPORTS = {
     "kw_dtw_workspace": (ctypes.c_size_t, [c_i64, c_i64, c_i64]),
     "kw_repeat_process": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, ctypes.c_float, c_i32, c_vp]),
     "kw_beam_logprobs_rep": (ctypes.c_int, [ctypes.POINTER(BeamLogprobsArgs), ctypes.c_float, c_i32, c_vp]),
+    "kw_seq_bias_process": (ctypes.c_int, [c_vp, c_i64, c_i64, c_vp, c_i64, c_vp, ctypes.POINTER(SeqBiasTable), c_vp]),
+    "kw_beam_logprobs_proc": (ctypes.c_int, [ctypes.POINTER(BeamLogprobsArgs), ctypes.c_float, c_i32,
+                                             ctypes.POINTER(SeqBiasTable), ctypes.POINTER(SeqBiasTable), c_vp]),
     "kw_beam_select_parents": (ctypes.c_int, [ctypes.POINTER(BeamSelectArgs), c_vp, c_vp, c_vp]),
     "kw_align_weights_rows": (ctypes.c_int, [ctypes.c_int, c_vp, c_i64, c_i64, c_vp, c_vp, c_i64, c_i64,
                                              ctypes.POINTER(c_i32), c_i64, c_i64, c_i64, c_i64, c_i64, c_vp, c_vp]),

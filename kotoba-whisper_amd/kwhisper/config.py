@@ -143,6 +143,10 @@ class GenerationConstants:
     # not pass the keyword
     repetition_penalty: float | None = None
     no_repeat_ngram_size: int | None = None
+    # SequenceBiasLogitsProcessor / NoBadWordsLogitsProcessor (None = off): ``{(ids...): float}`` or the list form
+    # ``[[ids], float]`` a generation_config.json stores; a list of token-id lists.  Read as the two above
+    sequence_bias: dict | list | None = None
+    bad_words_ids: list | None = None
 
     @property
     def timestamp_begin(self) -> int:

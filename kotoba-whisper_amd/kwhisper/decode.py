@@ -122,6 +122,7 @@ class DecodeSession:
         # split-row sampler partials + per-row arrival counters (zeroed once; kernels leave them zeroed)
         self.samp_ws = torch.zeros((ops.greedy_step_workspace_bytes(R) + 3) // 4, device=dev, dtype=torch.float32)
         self._greedy_cfg = {}
+        self._seq_dev = {}  # sequence_bias / bad_words_ids tables on the device, by content digest
         self._pinned = None
         self._lmg_ws = None  # kw_dec_lm_greedy's partials + arrival counter (zeroed once; launches re-arm it)
         self.lm_greedy_last = False
@@ -617,7 +618,8 @@ class DecodeSession:
 
     def generate(self, prompt: torch.Tensor, gen, *, max_length: int, return_timestamps: bool,
                  check_every: int = 4, use_graph: bool = True, record_scores: bool = False, align=None,
-                 num_frames=None, median_filter_width: int = 7, sample=None, key_start=None, repeat=None):
+                 num_frames=None, median_filter_width: int = 7, sample=None, key_start=None, repeat=None,
+                 seq_tables=None):
         """Greedy loop of GenerationMixin._sample (TF/generation/utils.py:2783-2941).
 
         ``sample``: None (the greedy path, unchanged), or a dict -- ``temperature`` (0 = argmax), ``seed``, ``attempt``
@@ -646,8 +648,16 @@ class DecodeSession:
         keys and launches.  Otherwise kw_repeat_process runs on the raw logits between the LM head and the greedy /
         sampled step -- in the prefill too (the first token is penalised against the prompt) and in every step, on the
         same stream -- so the step's tail is never the fused LM-head + greedy launch.  With ``record_scores`` the
-        logits recorded per step are the penalised ones; ``self.raw_logits`` keeps the LM head's own."""
+        logits recorded per step are the penalised ones; ``self.raw_logits`` keeps the LM head's own.
+
+        ``seq_tables``: (sequence_bias, bad_words_ids) as ``seq_bias.SeqTable`` or None each, or None.  None / both
+        None: exactly today's plans, graph keys and launches.  Otherwise kw_seq_bias_process runs in the same place --
+        the sequence_bias table ahead of kw_repeat_process, the bad_words_ids table behind it (TF generation/utils.py:
+        1154-1155, 1207-1213) -- in the prefill and in every step, so the tail is never the fused LM-head + greedy
+        launch.  The tables' digests are part of the plan / graph key: a captured graph holds the device arrays'
+        addresses, and a call with other values gets its own arrays, plans and graphs."""
         repeat = _norm_repeat(repeat)
+        seq_dev = self._seq_tables(seq_tables)
         masked = self._set_key_start(key_start)
         self._keep_prefill(prompt.shape[1])
         if masked and align is not None:
@@ -705,6 +715,8 @@ class DecodeSession:
             key += ("masked",)
         if repeat is not None:
             key += (("repeat",) + repeat,)
+        if seq_dev is not None:
+            key += (("seq",) + tuple(t and t.digest for t in seq_dev),)
         cfg = self._greedy_cfg.get(key)
         if cfg is None:
             sup = torch.zeros((self.eng.shape.vocab_size,), dtype=torch.uint8)
@@ -729,23 +741,33 @@ class DecodeSession:
             cfg = dict(sampler=sampler, score_buf=score_buf, graph=None, P=P)
             if repeat is not None:
                 cfg["repeat"] = ops.RepeatPlan(self.logits, self.ids, self.cur_len, penalty=repeat[0], ngram=repeat[1])
+            if seq_dev is not None:
+                cfg["seq"] = tuple(t and ops.SeqBiasPlan(self.logits, self.ids, self.cur_len, t) for t in seq_dev)
             if len(self._greedy_cfg) >= 8:  # bound the cache (each entry may hold a graph)
                 self._greedy_cfg.pop(next(iter(self._greedy_cfg)))
             self._greedy_cfg[key] = cfg
         sampler, score_buf = cfg["sampler"], cfg["score_buf"]
         self.scores = [] if record_scores else None
-        self.raw_logits = [] if record_scores and repeat is not None else None
+        self.raw_logits = [] if record_scores and (repeat is not None or seq_dev is not None) else None
         rep_plan = cfg.get("repeat")
+        sb_plan, bw_plan = cfg.get("seq", (None, None))
+        processed = rep_plan is not None or sb_plan is not None or bw_plan is not None
 
         def processed_tail(tail):
-            """The step's token choice, behind the repetition processors where the call has them."""
-            if rep_plan is None:
+            """The step's token choice, behind the GenerationMixin processors where the call has them: sequence_bias,
+            the repetition pair, bad_words_ids."""
+            if not processed:
                 return tail
 
             def run():
                 if self.raw_logits is not None:
                     self.raw_logits.append(self.logits.clone())
-                rep_plan()
+                if sb_plan is not None:
+                    sb_plan()
+                if rep_plan is not None:
+                    rep_plan()
+                if bw_plan is not None:
+                    bw_plan()
                 tail()
             return run
 
@@ -777,7 +799,7 @@ class DecodeSession:
         tail = sampler
         s = self.eng.shape
         if (self.eng.packed and self.nb == 1 and self.eng.fuse_lm_greedy and not return_timestamps and not record_scores
-                and sample is None and rep_plan is None and ops.lm_greedy_supported(B, s.vocab_size, s.d_model)):
+                and sample is None and not processed and ops.lm_greedy_supported(B, s.vocab_size, s.d_model)):
             tail = cfg.get("lm_greedy")
             if tail is None:
                 if self._lmg_ws is None:
@@ -923,7 +945,7 @@ class DecodeSession:
 
     def generate_beam(self, prompt: torch.Tensor, gen, *, num_beams: int, max_length: int, return_timestamps: bool,
                       length_penalty: float = 1.0, early_stopping=False, check_every: int = 4, use_graph: bool = True,
-                      repeat=None, align=None, num_frames=None, median_filter_width: int = 7):
+                      repeat=None, align=None, num_frames=None, median_filter_width: int = 7, seq_tables=None):
         """``GenerationMixin._beam_search`` (TF/generation/utils.py:3208-3527) on device, num_return_sequences 1.
 
         ``prompt`` (B, P) per item.  Returns host int64 (B, P + generated) -- the best finished beam of each
@@ -939,8 +961,13 @@ class DecodeSession:
         host backtraces the returned hypotheses to the reference's ``beam_indices`` (``beam_backtrace``), turns them
         into the row table of TF generation_whisper.py:265-301 (``beam_row_table``) and the alignment stage reads the
         log through it (kw_align_weights_rows).  ``self.align_out`` is laid out as the greedy path's -- ``frames``
-        int32 (B, W - 1), W the longest returned hypothesis in generated tokens -- plus ``beam_indices`` (B, W)."""
+        int32 (B, W - 1), W the longest returned hypothesis in generated tokens -- plus ``beam_indices`` (B, W).
+
+        ``seq_tables``: (sequence_bias, bad_words_ids) tables as in ``generate``.  None / both None: exactly today's
+        plan and graphs.  Otherwise kw_beam_logprobs_proc is the launch: the bias is added to every row's log-probs
+        ahead of the repetition pair, the bad words join the n-gram bans behind it."""
         repeat = _norm_repeat(repeat)
+        seq_dev = self._seq_tables(seq_tables)
         B, nb, R = self.B, self.nb, self.R
         if nb != num_beams or nb < 2:
             raise ValueError("session beam width mismatch")
@@ -967,6 +994,8 @@ class DecodeSession:
                gen.no_timestamps_token_id, gen.eos_token_id, gen.max_initial_timestamp_index)
         if repeat is not None:
             key += (("repeat",) + repeat,)
+        if seq_dev is not None:
+            key += (("seq",) + tuple(t and t.digest for t in seq_dev),)
         if align is not None:
             key += (("align",) + align,)
         cfg = self._greedy_cfg.get(key)
@@ -1000,7 +1029,8 @@ class DecodeSession:
                                     no_ts_id=gen.no_timestamps_token_id, eos_id=gen.eos_token_id,
                                     max_initial_ts=gen.max_initial_timestamp_index, begin_index=P,
                                     max_length=max_length, fill_id=fill, length_penalty=length_penalty,
-                                    early_stopping=early_stopping, repeat=repeat)
+                                    early_stopping=early_stopping, repeat=repeat,
+                                    **({} if seq_dev is None else {"seq_tables": seq_dev}))
             cfg = dict(st=st, step=step, graph=None, prefill_graph=None, P=P)
             if len(self._greedy_cfg) >= 8:
                 self._greedy_cfg.pop(next(iter(self._greedy_cfg)))
@@ -1064,6 +1094,32 @@ class DecodeSession:
             self.align_out = self._alignment(align, table.shape[1], num_frames, median_filter_width, rows=table)
             self.align_out["beam_indices"] = bi
         return out[:, : P + int(fin_len.max())]
+
+
+    def _seq_tables(self, seq_tables):
+        """``seq_tables`` -- (sequence_bias, bad_words_ids) host tables, None each -- as device tables, or None when
+        there is neither.  A table goes to the device once per content (its digest) and stays while a plan may hold
+        its addresses: the few most recent are kept here, every plan keeps its own besides."""
+        if seq_tables is None:
+            return None
+        sb, bw = seq_tables
+        if (sb is None or len(sb) == 0) and (bw is None or len(bw) == 0):
+            return None
+        V = self.eng.shape.vocab_size
+        out = []
+        for t in (sb, bw):
+            if t is None or len(t) == 0:
+                out.append(None)
+                continue
+            if int(t.tokens.max()) >= V:  # (generate() raises the reference's error before it gets here)
+                raise ValueError(f"sequence table token ids must be below the vocabulary size {V}")
+            d = self._seq_dev.get(t.digest)
+            if d is None:
+                if len(self._seq_dev) >= 16:
+                    self._seq_dev.pop(next(iter(self._seq_dev)))
+                d = self._seq_dev[t.digest] = ops.DeviceSeqTable(t, self.eng.device)
+            out.append(d)
+        return tuple(out)
 
 
 def beam_backtrace(parent_log: np.ndarray, fin_parent: np.ndarray, fin_len: np.ndarray, begin_index: int) -> np.ndarray:

@@ -36,6 +36,12 @@ TF/models/whisper/generation_whisper.py:383-968):
                                               TF/generation/utils.py:1174-1183, TF/generation/logits_process.py:406-413, 1121-1139
     ``generate_multitask``, ``pseudo_label*`` and ``ASRPipeline(generate_kwargs=...)`` forward their keywords to
     ``generate`` unchanged, so the two reach it from there as well.
+  * ``sequence_bias`` / ``bad_words_ids`` (from the call, else the generation config): SequenceBiasLogitsProcessor
+    immediately ahead of that pair, NoBadWordsLogitsProcessor immediately behind it, both ahead of the Whisper
+    processors, on device in every step of every pass and every fallback attempt -- kw_seq_bias_process on the raw
+    logits (csrc/seqbias.hip), kw_beam_logprobs_proc on the log-probs for beams (csrc/beam.hip); the host flattens
+    each processor into a table once (kwhisper/seq_bias.py)
+                                              TF/generation/utils.py:1154-1155, 1207-1213, TF/generation/logits_process.py:1288-1319, 1450-1467
   * ``assistant_model`` / ``num_assistant_tokens``: assisted (speculative) decoding at batch size 1 -- per seek pass
     the assistant (another ``KWhisperForConditionalGeneration``) encodes the features with its own encoder and drafts
     K tokens with its greedy step, this model checks them in one K + 1-position forward and ``kw_spec_accept``
@@ -79,6 +85,7 @@ import numpy as np
 import torch
 
 from .config import PRESETS, GenerationConstants, WhisperShape, generation_constants, language_to_id
+from . import seq_bias
 from .engine import WhisperEngine
 
 _SUPPORTED = {
@@ -90,6 +97,7 @@ _SUPPORTED = {
     "synced_gpus", "force_unique_generate_call", "prefix_allowed_tokens_fn", "prompt_condition_type",
     "monitor_progress", "use_cache", "num_return_sequences", "length_penalty", "early_stopping",
     "repetition_penalty", "no_repeat_ngram_size", "assistant_model", "num_assistant_tokens",
+    "sequence_bias", "bad_words_ids",
 }
 
 
@@ -393,6 +401,7 @@ class KWhisperForConditionalGeneration:
             gen = GenerationConstants(**gen)
         num_beams = kwargs.get("num_beams", gen.num_beams or 1)
         repeat = _repeat_arguments(kwargs, gen)
+        seq_tables = _sequence_arguments(kwargs, gen, self.engine.shape.vocab_size)
         # decoding fallback: the thresholds from the call or the generation config (_set_thresholds_and_condition,
         # generation_whisper.py:1703-1729) and the temperature schedule (:735); `do_sample` itself is overridden by
         # the schedule (:1002-1010)
@@ -458,7 +467,7 @@ class KWhisperForConditionalGeneration:
         num_assist = 0
         if assistant is not None:
             num_assist = _assistant_arguments(self, assistant, kwargs, num_beams=num_beams, fallback=fallback,
-                                              prompted=prompted, repeat=repeat)
+                                              prompted=prompted, repeat=repeat, seq_tables=seq_tables)
             gen.begin_suppress_tokens = None  # dropped with an assistant (generation_whisper.py:718-720)
         length_penalty = kwargs.get("length_penalty", getattr(gen, "length_penalty", 1.0))
         early_stopping = kwargs.get("early_stopping", getattr(gen, "early_stopping", False))
@@ -630,6 +639,8 @@ class KWhisperForConditionalGeneration:
                 sess.set_encoder_output(enc, key=enc_key)
             skip = [False] * cur
             rep_kw = {} if repeat is None else {"repeat": repeat}  # (None: the session calls as they ever were)
+            if seq_tables is not None:
+                rep_kw["seq_tables"] = seq_tables
             if assistant is not None:
                 ids = sess.generate(torch.from_numpy(prompt), gen, K=num_assist, max_length=eff_max,
                                     return_timestamps=return_timestamps)
@@ -641,7 +652,8 @@ class KWhisperForConditionalGeneration:
                         and self._sot_logits.shape[0] == cur:
                     sot = self._sot_logits  # language detection ran this very position on these features
                 ids, skip, attempts = self._generate_with_fallback(sess, prompt, gen, eff_max, return_timestamps,
-                                                                   temperatures, thr, batch_map, sot, key_start, repeat)
+                                                                   temperatures, thr, batch_map, sot, key_start, repeat,
+                                                                   seq_tables)
                 fallback_log.append(attempts)
                 for rec in attempts:  # (:1088-1093): a row accepted at a temperature of 0.5 or more loses its conditioning
                     for p in rec["rows"]:
@@ -724,13 +736,13 @@ class KWhisperForConditionalGeneration:
         return res
 
     def _generate_with_fallback(self, sess, prompt, gen, max_length, return_timestamps, temperatures, thr, batch_map,
-                                sot_logits=None, key_start=None, repeat=None):
+                                sot_logits=None, key_start=None, repeat=None, seq_tables=None):
         """One seek pass's attempt loop (``generate_with_fallback``, generation_whisper.py:1001-1116): decode at each
         temperature of the schedule in turn -- 0 greedy, above 0 sampled -- re-decoding only the rows whose
         ``_need_fallback`` decision asks for it, in the same session (its cross K/V stays; no re-encode); the last
         temperature's result is accepted.  Returns the pass's ids (cur, L) with every row from the attempt that was
         accepted for it (right-padded), the rows to skip, and the per-attempt record kept in ``stats["fallback"]``.
-        ``repeat`` goes to every attempt (the reference copies the generation config per attempt)."""
+        ``repeat`` and ``seq_tables`` go to every attempt (the reference copies the generation config per attempt)."""
         cur, P = prompt.shape
         pad, eos, V = gen.pad_token_id, gen.eos_token_id, self.engine.shape.vocab_size
         nsp = None
@@ -748,6 +760,7 @@ class KWhisperForConditionalGeneration:
             ids = sess.generate(torch.from_numpy(prompt), gen, max_length=max_length, return_timestamps=return_timestamps,
                                 **({} if key_start is None else {"key_start": key_start}),
                                 **({} if repeat is None else {"repeat": repeat}),
+                                **({} if seq_tables is None else {"seq_tables": seq_tables}),
                                 sample=dict(temperature=t, seed=self._seed, active=active,
                                             attempt=(self._lane << 24) | (self._attempts & 0xFFFFFF)))
             rec = dict(rows=[int(batch_map[i]) for i in rows], temperature=float(t), avg_logprob=[], compression_ratio=[],
@@ -860,7 +873,7 @@ class KWhisperForConditionalGeneration:
         return np.broadcast_to(arr, (B, arr.shape[1])).copy()
 
 
-def _assistant_arguments(model, assistant, kwargs, *, num_beams, fallback, prompted, repeat) -> int:
+def _assistant_arguments(model, assistant, kwargs, *, num_beams, fallback, prompted, repeat, seq_tables=None) -> int:
     """Check an ``assistant_model`` call and return K, the constant number of tokens drafted per round: from the call
     (``num_assistant_tokens``), else the assistant's generation config, else 5."""
     if not isinstance(assistant, KWhisperForConditionalGeneration):
@@ -871,6 +884,7 @@ def _assistant_arguments(model, assistant, kwargs, *, num_beams, fallback, promp
                      (bool(kwargs.get("return_token_timestamps")), "`return_token_timestamps`"),
                      (prompted, "`prompt_ids` / `condition_on_prev_tokens`"),
                      (repeat is not None, "`repetition_penalty` / `no_repeat_ngram_size`"),
+                     (seq_tables is not None, "`sequence_bias` / `bad_words_ids`"),
                      (getattr(model.engine, "cross_kv_fp8", False) or getattr(assistant.engine, "cross_kv_fp8", False),
                       "cross_kv_dtype='fp8_e4m3'")):
         if on:
@@ -887,6 +901,24 @@ def _assistant_arguments(model, assistant, kwargs, *, num_beams, fallback, promp
     if not isinstance(K, int) or isinstance(K, bool) or not 1 <= K <= 31:
         raise ValueError(f"`num_assistant_tokens` has to be an integer in [1, 31], but is {K}")
     return K
+
+
+def _sequence_arguments(kwargs, gen, vocab_size):
+    """``sequence_bias`` / ``bad_words_ids`` from the call, else the generation config, as the ``seq_tables`` pair of
+    ``DecodeSession.generate`` -- None when neither processor would be built (TF generation/utils.py:1154-1155,
+    1207-1213).  The values are checked as the processors check them (``ValueError``), token ids against the
+    vocabulary as their first call does, the sizes against the engine's caps (``NotImplementedError``); bad words
+    equal to ``[eos]`` are dropped, and a list that ends empty is no argument."""
+    sb = kwargs.get("sequence_bias")
+    if sb is None:
+        sb = getattr(gen, "sequence_bias", None)
+    bw = kwargs.get("bad_words_ids")
+    if bw is None:
+        bw = getattr(gen, "bad_words_ids", None)
+    if sb is None and bw is None:
+        return None
+    sb, bw = seq_bias.build_tables(sb, bw, gen.eos_token_id, vocab_size)
+    return None if sb is None and bw is None else (sb, bw)
 
 
 def _repeat_arguments(kwargs, gen):

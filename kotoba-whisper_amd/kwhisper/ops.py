@@ -5,7 +5,7 @@ ops wrap the ABI"), which fills the C ABI's argument block and launches on torch
 the kernels are ordinary torch ops to the dispatcher, to ``torch.cuda.graph`` capture and to
 ``torch.compile`` (fake implementations are registered: every op mutates its outputs and returns nothing).
 Tensors are plumbing only (device memory + stream); all arithmetic happens in the HIP kernels of
-``libkwhisper.so``.  The plan classes (``GemmPlan``, ``DecLinearPlan``, ``SamplerPlan``, ``SamplePlan``, ``SpecAcceptPlan``, ``RepeatPlan``, ``BeamStepPlan``)
+``libkwhisper.so``.  The plan classes (``GemmPlan``, ``DecLinearPlan``, ``SamplerPlan``, ``SamplePlan``, ``SpecAcceptPlan``, ``RepeatPlan``, ``SeqBiasPlan``, ``BeamStepPlan``)
 validate once and keep the op arguments, so decode steps replay without re-validation.
 
 ``set_backend("ctypes")`` routes the same calls through the ctypes binding of the C ABI instead (used by
@@ -878,16 +878,68 @@ class RepeatPlan:
                                              ctypes.c_void_p(a[5]), a[6], a[7], _s()), "kw_repeat_process")
 
 
+class DeviceSeqTable:
+    """A ``seq_bias.SeqTable`` on the device: the five arrays of ``kw_seq_bias_table`` as tensors, and the struct the
+    ctypes binding passes.  ``digest`` is the host table's (plans and graphs are keyed by it)."""
+
+    def __init__(self, table, device):
+        if len(table) == 0:
+            raise ValueError("an empty sequence table is no table (pass None)")
+        self.digest, self.max_len = table.digest, int(table.max_len)
+        self.n_seq, self.n_groups = int(table.n_seq), int(table.n_groups)
+        self.tensors = [torch.from_numpy(a.copy()).to(device) for a in table.arrays()]
+        c = L.SeqBiasTable()
+        c.tokens, c.seq_off, c.values, c.group_off, c.group_tok = (t.data_ptr() for t in self.tensors)
+        c.n_seq, c.n_groups, c.max_len = self.n_seq, self.n_groups, self.max_len
+        self.c = c
+        self.ref = ctypes.byref(c)
+
+
+class SeqBiasPlan:
+    """Pre-built ``kw_seq_bias_process`` call: one sequence table (``sequence_bias``, or ``bad_words_ids`` as -inf
+    values) in place on the f32 ``scores`` [R][V], from every row's history ``ids[r][0 .. *cur_len)`` (the device
+    scalar, so a captured step replays).  ``sequence_bias`` runs ahead of ``RepeatPlan``, ``bad_words_ids`` behind it,
+    both ahead of ``SamplerPlan`` / ``SamplePlan``."""
+
+    def __init__(self, scores, ids, cur_len, table: DeviceSeqTable):
+        _cuda(scores, ids, cur_len)
+        if scores.dim() != 2 or scores.dtype != torch.float32 or not scores.is_contiguous():
+            raise ValueError("kw_seq_bias_process: scores must be a contiguous (R, V) float32 tensor")
+        if (ids.dim() != 2 or ids.dtype != torch.int64 or ids.stride(1) != 1 or ids.shape[0] < scores.shape[0]
+                or cur_len.dtype != torch.int32 or cur_len.numel() < 1):
+            raise ValueError("kw_seq_bias_process: ids int64 [R][ids_stride], cur_len int32 [1]")
+        self._keep = (scores, ids, cur_len, table)
+        self._targs = (scores, ids, cur_len, table.tensors, table.max_len)
+        R, V = scores.shape
+        self._cargs = (scores.data_ptr(), R, V, ids.data_ptr(), ids.stride(0), cur_len.data_ptr())
+
+    def __call__(self):
+        if _BACKEND == "torch":
+            _kw().seq_bias_process(*self._targs)
+        else:
+            a = self._cargs
+            L.check(_lib().kw_seq_bias_process(ctypes.c_void_p(a[0]), a[1], a[2], ctypes.c_void_p(a[3]), a[4],
+                                               ctypes.c_void_p(a[5]), self._keep[3].ref, _s()), "kw_seq_bias_process")
+
+
 class BeamStepPlan:
     """Pre-built ``kw_beam_logprobs`` + ``kw_beam_select`` calls for one beam-search step.  ``repeat`` = (penalty,
     ngram): ``kw_beam_logprobs_rep`` takes ``kw_beam_logprobs``'s place (None: exactly the plain launch).  A state
     that holds ``parent_log`` (int32 [max_length][R]) and ``fin_parent`` (int32 [B][nb]) selects
-    ``kw_beam_select_parents``, which also fills those two; without them the launch is ``kw_beam_select``."""
+    ``kw_beam_select_parents``, which also fills those two; without them the launch is ``kw_beam_select``.
+    ``seq_tables`` = (sequence_bias, bad_words_ids) as ``DeviceSeqTable`` or None each: with one of them
+    ``kw_beam_logprobs_proc`` is the launch (both None: exactly the launch without the argument)."""
 
     def __init__(self, st, logits, suppress_mask, begin_suppress, *, return_timestamps, ts_begin, no_ts_id, eos_id,
-                 max_initial_ts, begin_index, max_length, fill_id, length_penalty, early_stopping, repeat=None):
+                 max_initial_ts, begin_index, max_length, fill_id, length_penalty, early_stopping, repeat=None,
+                 seq_tables=None):
         """``st``: a dict of the device state tensors (see DecodeSession.generate_beam)."""
         self._rep = None if repeat is None else check_repeat(*repeat)
+        self._seq = None
+        if seq_tables is not None and (seq_tables[0] is not None or seq_tables[1] is not None):
+            self._seq = tuple(seq_tables)
+            if self._rep is None:
+                self._rep = (1.0, 0)
         self._keep = (st, logits, suppress_mask, begin_suppress)
         R, V = logits.shape
         B, nb = st["fin_score"].shape
@@ -956,7 +1008,15 @@ class BeamStepPlan:
                     "kw_beam_select_parents")
 
     def __call__(self):
-        if _BACKEND == "torch":
+        if self._seq is not None:
+            sb, bw = self._seq
+            if _BACKEND == "torch":
+                _kw().beam_logprobs_proc(*self._tlp, *self._rep, sb.tensors if sb else [], sb.max_len if sb else 0,
+                                         bw.tensors if bw else [], bw.max_len if bw else 0)
+            else:
+                L.check(_lib().kw_beam_logprobs_proc(self._ra, self._rep[0], self._rep[1], sb.ref if sb else None,
+                                                     bw.ref if bw else None, _s()), "kw_beam_logprobs_proc")
+        elif _BACKEND == "torch":
             kw = _kw()
             if self._rep is None:
                 kw.beam_logprobs(*self._tlp)

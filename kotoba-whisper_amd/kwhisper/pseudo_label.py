@@ -174,7 +174,13 @@ def run_digest(model, **config) -> str:
     fp = weights_fingerprint(model)
     if fp is not None:
         ident["weights"] = fp
-    blob = json.dumps({"model": ident, **config}, sort_keys=True, default=repr)
+    gk = config.get("gen_kwargs")
+    if isinstance(gk, dict) and gk.get("sequence_bias") is not None:
+        # a dict with tuple keys is no JSON; the dict form and the list form of one bias are one configuration
+        from .seq_bias import canonical_sequence_bias
+
+        config = dict(config, gen_kwargs=dict(gk, sequence_bias=canonical_sequence_bias(gk["sequence_bias"])))
+    blob =json.dumps({"model": ident, **config}, sort_keys=True, default=repr)
     return hashlib.sha256(blob.encode()).hexdigest()
 
 
