@@ -147,12 +147,14 @@ size_t kw_packed_weight_bytes(int64_t N, int64_t K);
 /* LayerNorm (eps) over the last dim of x [rows][dim] f32 -> y [rows][dim] (y_dtype);
  * TF modeling_whisper.py:371,377,434,443,446,642,790. dim % 4 == 0, dim <= 2048.  delta (bf16
  * [rows][dim] or NULL): the producing linear's output, added to x in place first (the residual add
- * of :398,407 fused in front of the next LayerNorm). */
+ * of :398,407 fused in front of the next LayerNorm).  gamma, beta: [dim] f32.  x, gamma, beta and an f32 y
+ * must be 16-B aligned, delta and a bf16 y 8-B aligned (the widths of the kernel's accesses); anything else
+ * returns KW_EINVAL.  rows == 0 returns KW_OK and launches nothing. */
 int kw_layernorm(float* x, int64_t rows, int64_t dim, const float* gamma, const float* beta,
                  float eps, void* y, int y_dtype, const void* delta, kw_stream_t stream);
 /* The same over a bf16 residual stream x [rows][dim] (the encoder's bf16 path): x += delta is rounded
- * to bf16, as the reference's residual add in a bf16 model is. dim % 8 == 0, dim <= 2048, x/y/delta
- * 16-B aligned. */
+ * to bf16, as the reference's residual add in a bf16 model is. dim % 8 == 0, dim <= 2048; x, y, delta,
+ * gamma and beta 16-B aligned (KW_EINVAL otherwise). */
 int kw_layernorm_bf16res(void* x, int64_t rows, int64_t dim, const float* gamma, const float* beta,
                          float eps, void* y, int y_dtype, const void* delta, kw_stream_t stream);
 

@@ -242,6 +242,11 @@ extern "C" int kw_layernorm(float* x, int64_t rows, int64_t dim, const float* ga
                             float eps, void* y, int y_dtype, const void* delta, kw_stream_t stream) {
   if (!x || !gamma || !beta || !y || rows < 0 || dim <= 0 || dim % 4 != 0 || dim > 64 * 4 * LN_MAXV)
     return kw_set_error_msg(KW_EINVAL, "kw_layernorm: invalid arguments (dim % 4 == 0, dim <= 2048)");
+  // 16-B accesses of x, gamma, beta and an f32 y; 8-B accesses of delta and a bf16 y
+  if ((uintptr_t)x % 16 != 0 || (uintptr_t)gamma % 16 != 0 || (uintptr_t)beta % 16 != 0 ||
+      (uintptr_t)y % (y_dtype == KW_DT_F32 ? 16 : 8) != 0 || (delta && (uintptr_t)delta % 8 != 0))
+    return kw_set_error_msg(KW_EINVAL, "kw_layernorm: x, gamma, beta and an f32 y must be 16-B aligned, delta and a "
+                                       "bf16 y 8-B aligned");
   if (rows == 0) return KW_OK;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)((rows + 3) / 4));
@@ -258,8 +263,10 @@ extern "C" int kw_layernorm(float* x, int64_t rows, int64_t dim, const float* ga
 extern "C" int kw_layernorm_bf16res(void* x, int64_t rows, int64_t dim, const float* gamma, const float* beta,
                                     float eps, void* y, int y_dtype, const void* delta, kw_stream_t stream) {
   if (!x || !gamma || !beta || !y || rows < 0 || dim <= 0 || dim % 8 != 0 || dim > 64 * 8 * LNB_MAXV ||
-      (uintptr_t)x % 16 != 0 || (uintptr_t)y % 16 != 0 || (delta && (uintptr_t)delta % 16 != 0))
-    return kw_set_error_msg(KW_EINVAL, "kw_layernorm_bf16res: invalid arguments (dim % 8 == 0, dim <= 2048, 16-B aligned)");
+      (uintptr_t)x % 16 != 0 || (uintptr_t)y % 16 != 0 || (delta && (uintptr_t)delta % 16 != 0) ||
+      (uintptr_t)gamma % 16 != 0 || (uintptr_t)beta % 16 != 0)
+    return kw_set_error_msg(KW_EINVAL, "kw_layernorm_bf16res: invalid arguments (dim % 8 == 0, dim <= 2048, x, y, delta, "
+                                       "gamma and beta 16-B aligned)");
   if (rows == 0) return KW_OK;
   hipStream_t s = (hipStream_t)stream;
   dim3 grid((unsigned)((rows + 3) / 4));

@@ -173,7 +173,17 @@ void layernorm(Tensor& x, const Tensor& gamma, const Tensor& beta, double eps, T
   dev(x, w), dev(gamma, w), dev(beta, w), dev(y, w), dev(delta, w);
   TORCH_CHECK_VALUE(x.is_contiguous() && (x.scalar_type() == at::kFloat || x.scalar_type() == at::kBFloat16),
                     "layernorm input must be contiguous float32 or bfloat16");
-  const int64_t dim = x.size(-1), rows = x.numel() / dim;
+  const int64_t dim = x.dim() ? x.size(-1) : 0, rows = dim ? x.numel() / dim : 0;
+  for (const Tensor* t : {&gamma, &beta})
+    TORCH_CHECK_VALUE(t->scalar_type() == at::kFloat && t->numel() == dim && t->is_contiguous(),
+                      "layernorm gamma and beta must be contiguous float32 tensors of x's last dimension");
+  TORCH_CHECK_VALUE((y.scalar_type() == at::kFloat || y.scalar_type() == at::kBFloat16) && y.numel() == x.numel() &&
+                        y.is_contiguous(),
+                    "layernorm out must be a contiguous float32 or bfloat16 tensor of x's size");
+  TORCH_CHECK_VALUE(!delta.has_value() || (delta->scalar_type() == at::kBFloat16 && delta->numel() == x.numel() &&
+                                           delta->is_contiguous()),
+                    "layernorm delta must be a contiguous bf16 tensor of x's size");
+  if (rows == 0) return;  // nothing to launch (an empty tensor has no address to pass either)
   c10::DeviceGuard g(x.device());
   if (x.scalar_type() == at::kBFloat16)
     check(kw_layernorm_bf16res(ptr(x), rows, dim, ptr<const float>(gamma), ptr<const float>(beta), (float)eps, ptr(y),

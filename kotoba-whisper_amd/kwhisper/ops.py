@@ -123,10 +123,17 @@ def layernorm(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, eps: flo
         raise ValueError("layernorm input must be contiguous float32 or bfloat16")
     if delta is not None and (delta.dtype != torch.bfloat16 or delta.numel() != x.numel() or not delta.is_contiguous()):
         raise ValueError("layernorm delta must be a contiguous bf16 tensor of x's size")
-    if _BACKEND == "torch":
+    if _BACKEND == "torch":  # (the operator makes the checks below itself: csrc/torch_ops.cpp)
         _kw().layernorm(x, gamma, beta, float(eps), out, delta)
         return out
-    dim = x.shape[-1]
+    dim = x.shape[-1] if x.dim() else 0
+    for t in (gamma, beta):
+        if t.dtype != torch.float32 or t.numel() != dim or not t.is_contiguous():
+            raise ValueError("layernorm gamma and beta must be contiguous float32 tensors of x's last dimension")
+    if out.dtype not in (torch.float32, torch.bfloat16) or out.numel() != x.numel() or not out.is_contiguous():
+        raise ValueError("layernorm out must be a contiguous float32 or bfloat16 tensor of x's size")
+    if x.numel() == 0:  # no rows: nothing to launch (an empty tensor has no address to pass either)
+        return out
     rows = x.numel() // dim
     if x.dtype == torch.bfloat16:
         L.check(_lib().kw_layernorm_bf16res(_p(x), rows, dim, _p(gamma), _p(beta), eps, _p(out), _dt(out), _p(delta),
